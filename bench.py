@@ -9,13 +9,19 @@ images: weak scaling, no data-path collective); the driver launches one process
 per GPU via torch.distributed.run, and `--gpus N` without a launcher spawns the
 N rank processes itself (before anything touches a GPU).
 
+A plain run (`--gpus N --steps K --warmup W`) sets up, settles, warms up, times
+the K steps, writes the last step's outputs if `--dump-outputs DIR` is given, and
+prints the line; everything else below (`roofline`, `cpu_baseline`, the PPM
+lines, `extra_configs`) is measured only with `--full` and is null / absent
+without it.
+
 Prints ONE JSON line on rank 0.  `value` comes from the timed region: the
 production path, every call launched directly (four kernels per frame: k_front,
 k_hist with the fused tables, k_emit with the fused offsets, k_stuffwrite),
 consecutive frames pipelined over the context's lanes, after an untimed settle
 phase of the same steps (--settle-ms, profiles/r06_settle_study.txt), the input frames rotating
 over enough distinct slots (> 256 MiB together) that their pixels stream from
-HBM rather than the 256 MiB Infinity Cache.  `roofline` comes from a second
+HBM rather than the 256 MiB Infinity Cache.  `roofline` (`--full`) comes from a second
 pass over the same steps, one frame at a time, with HIP events around every
 kernel launch, recorded on the stream the kernel runs on: per kernel the average
 launch duration, the SURVEY.md 8(d) algorithmic bytes over it, and the PMC
@@ -23,15 +29,20 @@ traffic from profiles/; the dominant (longest) kernel is the headline.
 `rocprofv3 --kernel-trace` of this command times the same dispatches:
 scripts/kstats_passes.py splits its trace into the settle phase and the two
 passes (profiles/r06_v01_kernel_passes.csv).
-`cpu_baseline` times the CPU restatement of the reference encoder (oracle/, C,
+`cpu_baseline` (`--full`) times the CPU restatement of the reference encoder (oracle/, C,
 the reference's DCT thread-pool structure) on a bounded sample of the same
 workload on this host.
-`extra_configs` (on by default; `--no-extras` skips it) measures, after the
+`extra_configs` (with `--full`; `--no-extras` skips it) measures, after the
 headline and on every rank, the BASELINE configs that shard over the GPUs: config
 4 (one 32768x32768 image as MCU-row stripes, with and without restart intervals,
 strong scaling) and config 5 (a stream of 8K 4:2:0 frames at q50/75/95, weak
-scaling), each with its own per-rank block -- so the one `--gpus N` run the
-driver makes per N covers configs 2, 4 and 5.
+scaling), each with its own per-rank block -- so one `--gpus N --full` run
+per N covers configs 2, 4 and 5.
+`--dump-outputs DIR` writes, on rank 0, what the last timed step left for its
+caller: `jpeg_len.npy` (float64, the byte length of every JPEG file of that step)
+and `jpeg_bytes.npy` (float32, the files' bytes one after the other; above
+DUMP_MAX_VALUES a fixed seeded sample of them in file order).  The synthetic
+inputs depend on the arguments alone, so two builds can be compared file for file.
 """
 import argparse
 import json
@@ -135,6 +146,8 @@ def run_striped(args, world, rank, local_rank, make_encoder, barrier_sync, xgrou
     # (strong scaling: each rank's rate is its stripe's pixels over its own time)
     elapsed, ranks = gather_ranks(elapsed, world, enc, w * (y1 - y0) * args.steps)
     line = None
+    if rank == 0 and args.dump_outputs:  # rank 0's stripe (N = 1: the whole file)
+        dump_outputs(args.dump_outputs, [np.frombuffer(enc.d2h(d_out, int(n)), np.uint8)])
     if rank == 0:
         cpu = None
         if args.cpu_seconds > 0:  # the oracle on a bounded stripe of the same image (256 pixel rows)
@@ -240,6 +253,7 @@ def run_extras(args, world, rank, local_rank, make_encoder, enc, barrier_sync, x
     out = {}
     sargs = argparse.Namespace(**vars(args))
     sargs.steps, sargs.warmup, sargs.cpu_seconds, sargs.gather = args.extra_steps, 2, 0, False
+    sargs.dump_outputs = None  # (the dump is the headline's)
     for name in EXTRA_STRIPED:
         sargs.config = name
         try:
@@ -256,6 +270,29 @@ def run_extras(args, world, rank, local_rank, make_encoder, enc, barrier_sync, x
         if rank == 0:
             out[name] = line
     return out
+
+
+DUMP_MAX_VALUES = 15_000_000  # float32 values of jpeg_bytes.npy: 60 MB, the whole dump under 64 MB
+
+
+def dump_outputs(out_dir, files):
+    """--dump-outputs: `files` (one uint8 array per JPEG file the last timed step
+    wrote, each cut to its reported length) as out_dir/jpeg_len.npy (float64) and
+    out_dir/jpeg_bytes.npy (float32, the files joined; beyond DUMP_MAX_VALUES a
+    sample of the joined bytes at sorted positions drawn with a fixed seed)"""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "jpeg_len.npy"), np.array([f.size for f in files], np.float64))
+    joined = np.concatenate(files) if files else np.zeros(0, np.uint8)
+    if joined.size > DUMP_MAX_VALUES:
+        joined = joined[np.sort(np.random.default_rng(0).choice(joined.size, DUMP_MAX_VALUES, replace=False))]
+    np.save(os.path.join(out_dir, "jpeg_bytes.npy"), joined.astype(np.float32))
+
+
+def read_frames(enc, d_out, out_stride, d_len, n_frames):
+    """the JPEG files of one step back on the host: (lengths, [uint8 array per file])"""
+    lens = np.frombuffer(enc.d2h(d_len, 4 * n_frames), np.uint32)
+    return lens, [np.frombuffer(enc.d2h(d_out + k * out_stride, min(int(n), out_stride)), np.uint8)
+                  for k, n in enumerate(lens)]
 
 
 def gather_ranks(elapsed, world, enc, pixels_per_rank):
@@ -333,6 +370,10 @@ def run_inproc(args, emit, make_group):
     grp.synchronize()
     elapsed = time.perf_counter() - t0
     lens = np.frombuffer(mem[0].d2h(bufs[0][2][0], 4 * fps), np.uint32)
+    if args.dump_outputs:  # every member's files of the last step, member after member
+        last = (args.steps - 1) % lanes
+        dump_outputs(args.dump_outputs, [f for m, (_, d_out, d_len) in zip(mem, bufs)
+                                         for f in read_frames(m, d_out[last], out_stride, d_len[last], fps)[1]])
     ngpu = len(set(ids))
     value = n * w * h * fps * args.steps / elapsed / 1e6
     line = {
@@ -648,13 +689,18 @@ def main(argv=None, make_encoder=None, emit=None, make_group=None):
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="4k444q90", choices=sorted(CONFIGS) + sorted(STRIPED))
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the roofline and one-lane passes, the PPM lines, the CPU "
+                         "baseline and extra_configs (a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the JPEG files of the last timed step as DIR/jpeg_len.npy and DIR/jpeg_bytes.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU baseline budget (0 = skip)")
     ap.add_argument("--distinct-frames", type=int, default=0,
                     help="input slots the steps rotate over (0 = enough to exceed the 256 MiB Infinity Cache)")
     ap.add_argument("--mall-compare", action="store_true",
                     help="also time the steps over 4 input slots (inputs resident in the Infinity Cache)")
     ap.add_argument("--ppm-steps", type=int, default=20,
-                    help="PPM ingest line: P3 decodes of one synthetic frame timed on rank 0 (0 = skip)")
+                    help="--full: PPM ingest line: P3 decodes of one synthetic frame timed on rank 0 (0 = skip)")
     ap.add_argument("--gather", action="store_true",
                     help="striped configs, N>1: every step also sends the stripes to one file on rank 0 (RCCL p2p)")
     ap.add_argument("--lanes", type=int, default=4,
@@ -666,9 +712,9 @@ def main(argv=None, make_encoder=None, emit=None, make_group=None):
     ap.add_argument("--settle-ms", type=float, default=60.0,
                     help="untimed pipelined steps for this long before the warmup steps (0 = from cold)")
     ap.add_argument("--roofline-order", choices=("first", "last"), default="last",
-                    help="run the one-lane roofline pass before or after the timed region")
+                    help="--full: run the one-lane roofline pass before or after the timed region")
     ap.add_argument("--no-extras", dest="extras", action="store_false",
-                    help="skip extra_configs (BASELINE configs 4 and 5 after the headline)")
+                    help="--full: skip extra_configs (BASELINE configs 4 and 5 after the headline)")
     ap.add_argument("--extra-steps", type=int, default=5,
                     help="extra_configs: timed steps per striped config (x4 per 8K stream config)")
     ap.add_argument("--exchange", choices=("host", "device"), default="host",
@@ -679,6 +725,10 @@ def main(argv=None, make_encoder=None, emit=None, make_group=None):
                          "gather (RCCL refuses two ranks on one GPU); the line says so (ranks.devices)")
     args = ap.parse_args(argv)
     emit = emit or (lambda line: print(line, flush=True))
+    if not args.full:  # a plain run: nothing but what the headline figure needs
+        if args.roofline_order != "last":
+            raise SystemExit("bench: --roofline-order orders the roofline pass of a --full run")
+        args.cpu_seconds, args.ppm_steps, args.extras = 0.0, 0, False
     if args.inproc:
         if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) > 1:
             raise SystemExit("bench: --inproc drives every GPU from one process; do not launch it per rank")
@@ -775,7 +825,8 @@ def main(argv=None, make_encoder=None, emit=None, make_group=None):
         p = enc.profile()
         enc.set_profiling(0)
         return t, p
-    if args.roofline_order == "first":
+    single = single_plain = prof = None
+    if args.full and args.roofline_order == "first":
         single, prof = roofline_pass()
     # settle: the same pipelined steps, untimed, for --settle-ms of wall time before
     # the W warmup steps.  A fresh process runs its first few hundred 4K frames up to
@@ -795,11 +846,15 @@ def main(argv=None, make_encoder=None, emit=None, make_group=None):
     # timed region: the production path (no event timing inside); with lanes > 1
     # consecutive frames are pipelined over the context's lanes (dmmt_ctx_set_lanes)
     elapsed = timed(lanes)
-    if args.roofline_order == "last":
+    if args.dump_outputs and rank == 0:  # the last timed step's files, before a later pass rewrites them
+        last = (args.steps - 1) % lanes
+        dump_outputs(args.dump_outputs, read_frames(enc, d_out[last], out_stride, d_len[last], fps)[1])
+    if args.full and args.roofline_order == "last":
         single, prof = roofline_pass()
     # the same one-lane steps without the event records: a frame's latency on the
     # production path (the roofline pass's 8 event records per frame stretch it)
-    single_plain = timed(1)
+    if args.full:
+        single_plain = timed(1)
     extra = {}
     if args.mall_compare:  # inputs resident in the Infinity Cache: 4 slots
         extra["mall_resident_4_slots"] = timed(lanes, min(4, nslots))
@@ -823,7 +878,7 @@ def main(argv=None, make_encoder=None, emit=None, make_group=None):
                 pmc = json.load(open(pmc_path))
             except ValueError:
                 pmc = None
-        kern = kernel_roofline(prof, algo_bytes, fps, pmc)
+        kern = kernel_roofline(prof, algo_bytes, fps, pmc) if args.full else {}
         if "k_emit" in kern and "k_offsets" not in kern:  # frames of <= 6144 chunks
             kern["k_emit"]["includes"] = "the frame's chunk-offset scans (k_offsets fused into its last workgroup)"
         dom = max(kern, key=lambda k: kern[k]["avg_launch_us"]) if kern else None
@@ -856,8 +911,9 @@ def main(argv=None, make_encoder=None, emit=None, make_group=None):
             cfg["mall_resident_4_slots_value"] = round(pixels / world / t4 / 1e6, 2)
         # the roofline pass's wall time: one frame at a time, events on (the latency of
         # a frame plus the event records)
-        cfg["single_lane_ms_per_step"] = round(single / args.steps * 1e3, 4)
-        cfg["single_lane_plain_ms_per_step"] = round(single_plain / args.steps * 1e3, 4)
+        if args.full:
+            cfg["single_lane_ms_per_step"] = round(single / args.steps * 1e3, 4)
+            cfg["single_lane_plain_ms_per_step"] = round(single_plain / args.steps * 1e3, 4)
         line = {
             "metric": "Mpixel/s encoded (4K PPM, q=90)" if args.config == "4k444q90" else f"Mpixel/s encoded ({args.config})",
             "value": round(value, 2),
@@ -872,7 +928,7 @@ def main(argv=None, make_encoder=None, emit=None, make_group=None):
             "dtype": "f32",
             "data": "synthetic",
             "config": cfg,
-            "roofline": {
+            "roofline": None if not args.full else {
                 # bound: the roofline the fraction is priced against (no MFMA work:
                 # HBM); what limits the kernels is `limiter`
                 "bound": "hbm",

@@ -6,7 +6,7 @@ T=$1
 for spec in $2; do
   IFS=: read c K W <<< "$spec"
   O=gpurun_out/$T/$c; mkdir -p $O
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --config $c --steps $K --warmup $W --cpu-seconds 0 --ppm-steps 0 --no-extras > $O/bench_prof.json 2> $O/bench_prof.err || { echo "rocprof $c failed"; tail $O/bench_prof.err; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --config $c --steps $K --warmup $W --full --cpu-seconds 0 --ppm-steps 0 --no-extras > $O/bench_prof.json 2> $O/bench_prof.err || { echo "rocprof $c failed"; tail $O/bench_prof.err; exit 1; }
   f=$(ls $O/prof/*/run_kernel_stats.csv 2>/dev/null | head -1)
   [ -n "$f" ] || f=$(find $O/prof -name 'run_kernel_stats.csv' | head -1)
   cp $f $O/kernel_stats.csv

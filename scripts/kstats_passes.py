@@ -1,6 +1,6 @@
 """Per-kernel rocprofv3 durations of bench.py split into its passes.
 
-bench.py (default arguments) dispatches every k_* kernel S times in the untimed
+bench.py --full (otherwise default arguments) dispatches every k_* kernel S times in the untimed
 settle phase (config.settle.frames / config.frames_per_step of its line), W + K
 times in the pipelined timed pass, W + K times in the roofline pass (one step at
 a time, HIP events around each launch), then K times in the plain one-lane pass

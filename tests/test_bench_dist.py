@@ -103,7 +103,7 @@ def _worker(rank, world, port, out_dir):
     import bench
     log, lines = [], []
     bench.main(["--gpus", str(world), "--steps", "20", "--warmup", "2", "--cpu-seconds", "0", "--ppm-steps", "0",
-                "--config", "1080p420q75x256", "--no-extras"],
+                "--config", "1080p420q75x256", "--full", "--no-extras"],
                make_encoder=lambda lr: StandInEncoder(lr, rank, log), emit=lines.append)
     with open(os.path.join(out_dir, f"rank{rank}.json"), "w") as f:
         json.dump({"log": log, "lines": lines}, f)
@@ -190,7 +190,7 @@ def test_bench_line_fields_single_rank(monkeypatch):
         monkeypatch.delenv(k, raising=False)
     import bench
     log, lines = [], []
-    bench.main(["--steps", "5", "--warmup", "1", "--cpu-seconds", "0", "--ppm-steps", "0", "--no-extras"],
+    bench.main(["--steps", "5", "--warmup", "1", "--full", "--cpu-seconds", "0", "--ppm-steps", "0", "--no-extras"],
                make_encoder=lambda lr: StandInEncoder(lr, 0, log), emit=lines.append)
     line = json.loads(lines[0])
     assert line["n_gpus"] == 1 and line["metric"] == "Mpixel/s encoded (4K PPM, q=90)"
@@ -324,14 +324,14 @@ def _worker_extras(rank, world, port, out_dir):
     import bench
     log, lines = [], []
     bench.main(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--ppm-steps", "0",
-                "--extra-steps", "2"], make_encoder=lambda lr: StandInEncoder(lr, rank, log), emit=lines.append)
+                "--full", "--extra-steps", "2"], make_encoder=lambda lr: StandInEncoder(lr, rank, log), emit=lines.append)
     with open(os.path.join(out_dir, f"rank{rank}.json"), "w") as f:
         json.dump({"log": log, "lines": lines}, f)
 
 
 @pytest.mark.timeout(300)
 def test_bench_extra_configs_two_ranks(tmp_path):
-    """`bench.py --gpus 2` (the driver's SCALE command) prints configs 2, 4 and 5 in
+    """`bench.py --gpus 2 --full` (the SCALE command) prints configs 2, 4 and 5 in
     its one line: after the 4K headline, extra_configs holds BASELINE config 4 (the
     32768^2 image as one MCU-row stripe per rank, with restart intervals and
     joined) and config 5 (8K 4:2:0 streams at q50/75/95), each with its own ranks
@@ -374,6 +374,88 @@ def test_bench_no_extras_by_flag(monkeypatch):
         monkeypatch.delenv(k, raising=False)
     import bench
     lines = []
-    bench.main(["--steps", "2", "--warmup", "0", "--cpu-seconds", "0", "--ppm-steps", "0", "--no-extras"],
+    bench.main(["--steps", "2", "--warmup", "0", "--full", "--cpu-seconds", "0", "--ppm-steps", "0", "--no-extras"],
                make_encoder=lambda lr: StandInEncoder(lr, 0, []), emit=lines.append)
     assert "extra_configs" not in json.loads(lines[0])
+
+
+def test_bench_plain_run_is_lean(monkeypatch):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the settle phase and
+    the W + K pipelined steps, nothing after them (no one-lane pass, no PPM line, no
+    CPU baseline, no extra_configs), and the headline fields as with --full"""
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        monkeypatch.delenv(k, raising=False)
+    import bench
+    log, lines = [], []
+    calls = []
+
+    class Counting(StandInEncoder):
+        def encode_device(self, *a, **k):
+            calls.append(self.mask)
+            time.sleep(0.001)  # (so that ms_per_step's four decimals resolve the step)
+
+        def stripe_analyze(self, st, opts):
+            raise AssertionError("a plain run measures no striped config")
+
+    bench.main(["--gpus", "1", "--steps", "7", "--warmup", "3"], make_encoder=lambda lr: Counting(lr, 0, log),
+               emit=lines.append)
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert [x[2] for x in log if x[0] == "lanes"] == [4, 4]  # settle, then the timed region
+    settle = line["config"]["settle"]["frames"]
+    assert settle >= 32 and len(calls) == settle + 3 + 7 and not any(calls)  # (profiling never switched on)
+    assert line["metric"] == "Mpixel/s encoded (4K PPM, q=90)" and line["unit"] == "Mpixel/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f32" and line["steps"] == 7
+    assert line["value"] == pytest.approx(3840 * 2160 * 7 / (line["ms_per_step"] * 7 / 1e3) / 1e6, rel=2e-3)
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["ppm_ingest"] is None
+    assert "extra_configs" not in line and "single_lane_ms_per_step" not in line["config"]
+    with pytest.raises(SystemExit):  # an option of the --full passes alone is refused, not ignored
+        bench.main(["--steps", "1", "--roofline-order", "first"], make_encoder=lambda lr: Counting(lr, 0, log),
+                   emit=lines.append)
+
+
+def test_bench_dump_outputs(monkeypatch, tmp_path):
+    """--dump-outputs DIR: the files of the last timed step (its lane's buffers), each
+    cut to its reported length, as float64 lengths and float32 bytes; the same again
+    on a second run; a larger output is a fixed sample under the size cap"""
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        monkeypatch.delenv(k, raising=False)
+    import bench
+
+    class Files(StandInEncoder):
+        """every output buffer holds a 1000-byte file made of the buffer's handle"""
+
+        def d2h(self, d, n):
+            if n == 4 * 256:  # the step's 256 lengths
+                return np.full(256, 1000, np.uint32).tobytes()
+            return np.full(n, d % 251, np.uint8).tobytes()
+
+    out = []
+    for name in ("a", "b"):
+        encs = []
+
+        def make(lr):
+            encs.append(Files(lr, 0, []))
+            return encs[0]
+        bench.main(["--gpus", "1", "--steps", "6", "--warmup", "1", "--config", "1080p420q75x256",
+                    "--dump-outputs", str(tmp_path / name)], make_encoder=make, emit=lambda l: None)
+        lens = np.load(tmp_path / name / "jpeg_len.npy")
+        data = np.load(tmp_path / name / "jpeg_bytes.npy")
+        assert lens.dtype == np.float64 and data.dtype == np.float32
+        assert lens.tolist() == [1000.0] * 256 and data.shape == (256000,)
+        out.append(data)
+    assert np.array_equal(out[0], out[1])
+    # step 5 of 6 ran on lane 5 % 4 = 1: the second output buffer allocated (12 input slots
+    # of 256 1080p frames come first: handles 1..4 here, then the 4 lanes' outputs)
+    stride = (__import__("dmmt_jpeg").max_jpeg_bytes(1920, 1080, 2) + 255) // 256 * 256
+    nslots = max(4, bench.MALL_BYTES // (1920 * 1080 * 3 * 256) + 2)
+    assert out[0][:1000].tolist() == [float((nslots + 2) % 251)] * 1000
+    assert out[0][1000] == float((nslots + 2 + stride) % 251)
+    # above the cap: a sample of DUMP_MAX_VALUES bytes, the same positions every time
+    monkeypatch.setattr(bench, "DUMP_MAX_VALUES", 1000)
+    files = [np.arange(3000, dtype=np.uint32).astype(np.uint8), np.full(500, 7, np.uint8)]
+    bench.dump_outputs(str(tmp_path / "c"), files)
+    bench.dump_outputs(str(tmp_path / "d"), files)
+    c = np.load(tmp_path / "c" / "jpeg_bytes.npy")
+    assert c.shape == (1000,) and np.array_equal(c, np.load(tmp_path / "d" / "jpeg_bytes.npy"))
+    assert np.load(tmp_path / "c" / "jpeg_len.npy").tolist() == [3000.0, 500.0]
