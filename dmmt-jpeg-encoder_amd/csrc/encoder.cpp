@@ -401,10 +401,15 @@ int enqueue_back_half(dmmt_ctx* c, const Geom& g, int nf, const Work& w, int bit
 }
 
 int enqueue_direct(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, int nf, const Geom& g,
-                   const Work& w, int bits, uint8_t* out, size_t out_stride, uint32_t* out_len, hipStream_t st) {
+                   const Work& w, int bits, uint8_t* out, size_t out_stride, uint32_t* out_len, hipStream_t st,
+                   const Surface* sf = nullptr) {
     {
         StageTimer t(c, ST_FRONT, st);
-        HIP_TRY(launch_front(d_rgb, frame_stride, sb, nf, g, w, st, c->nlanes > 1 ? DMMT_FRONT_PER_CU_LANES : 0));
+        const int cap = c->nlanes > 1 ? DMMT_FRONT_PER_CU_LANES : 0;
+        if (sf)  // a surface: d_rgb is its first plane
+            HIP_TRY(launch_front_surface(*sf, frame_stride, sb, nf, g, w, st, cap));
+        else
+            HIP_TRY(launch_front(d_rgb, frame_stride, sb, nf, g, w, st, cap));
     }
     return enqueue_back_half(c, g, nf, w, bits, out, out_stride, out_len, st, sb == 4);
 }
@@ -419,7 +424,7 @@ void destroy_graphs(dmmt_ctx* c) {
 // Stage profiling needs per-kernel events, so it always launches directly.
 int enqueue_encode(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, int nf, const Geom& g,
                    const dmmt_options* opt, uint8_t* out, size_t out_stride, uint32_t* out_len, hipStream_t st,
-                   int lane = 0, bool async = false, int* status = nullptr) {
+                   int lane = 0, bool async = false, int* status = nullptr, const Surface* sf = nullptr) {
     Work w;
     int rc;
     if ((rc = prepare(c, g, nf, opt, sb, st, &w, lane, async, status))) return rc;
@@ -427,12 +432,16 @@ int enqueue_encode(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, 
     // (a per-file status area -- dmmt_convert_ppm_device_batch -- would put a new
     // pointer into every file's graph key: that path launches directly)
     if (!c->use_graphs || c->profile || status)
-        return enqueue_direct(c, d_rgb, frame_stride, sb, nf, g, w, bits, out, out_stride, out_len, st);
+        return enqueue_direct(c, d_rgb, frame_stride, sb, nf, g, w, bits, out, out_stride, out_len, st, sf);
     std::vector<uint64_t> key = {(uint64_t)(uintptr_t)d_rgb, (uint64_t)frame_stride, (uint64_t)sb, (uint64_t)nf,
                                  (uint64_t)g.width, (uint64_t)g.height, (uint64_t)g.hr, (uint64_t)g.vr,
                                  (uint64_t)g.maxval, (uint64_t)g.restart_interval, (uint64_t)bits,
                                  (uint64_t)(uintptr_t)out, (uint64_t)out_stride, (uint64_t)(uintptr_t)out_len,
-                                 (uint64_t)(uintptr_t)st};
+                                 (uint64_t)(uintptr_t)st,
+                                 // the layout: two surfaces may share their first pointer
+                                 sf ? (uint64_t)sf->format + 1 : 0, sf ? (uint64_t)sf->row_pitch : 0,
+                                 sf ? (uint64_t)(uintptr_t)sf->plane[0] : 0, sf ? (uint64_t)(uintptr_t)sf->plane[1] : 0,
+                                 sf ? (uint64_t)(uintptr_t)sf->plane[2] : 0};
     const void* const* wp = reinterpret_cast<const void* const*>(&w);
     static_assert(sizeof(Work) % sizeof(void*) == 0, "Work holds pointers only");
     for (size_t i = 0; i < sizeof(Work) / sizeof(void*); ++i) key.push_back((uint64_t)(uintptr_t)wp[i]);
@@ -442,7 +451,7 @@ int enqueue_encode(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, 
     if (!hit) {
         hipGraph_t graph = nullptr;
         HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        rc = enqueue_direct(c, d_rgb, frame_stride, sb, nf, g, w, bits, out, out_stride, out_len, st);
+        rc = enqueue_direct(c, d_rgb, frame_stride, sb, nf, g, w, bits, out, out_stride, out_len, st, sf);
         hipError_t e = hipStreamEndCapture(st, &graph);
         if (rc) {
             if (graph) (void)hipGraphDestroy(graph);
@@ -701,6 +710,31 @@ extern "C" size_t dmmt_max_jpeg_bytes(uint16_t width, uint16_t height, int32_t s
     return max_jpeg_bytes(g);
 }
 
+// dmmt_encode_device and dmmt_encode_device_surfaces (sf: the surface, whose
+// first plane is f->d_rgb) after their own argument checks
+static int encode_device_frames(dmmt_ctx* c, const dmmt_device_frames* f, const dmmt_options* opt, void* stream,
+                                const Geom& g, const Surface* sf) {
+    int rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    if (stream) {
+        // the caller's stream runs on lane 0's workspace: it waits for the work
+        // already queued on lane 0, and lane 0 for this call, in both directions
+        hipStream_t st = (hipStream_t)stream;
+        HIP_TRY(hipEventRecord(c->ev_lane0, c->stream));
+        HIP_TRY(hipStreamWaitEvent(st, c->ev_lane0, 0));
+        rc = enqueue_encode(c, f->d_rgb, f->frame_stride, f->sample_bytes, f->n_frames, g, opt, f->d_out,
+                            f->out_stride, f->d_out_len, st, 0, true, nullptr, sf);
+        HIP_TRY(hipEventRecord(c->ev_caller, st));
+        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_caller, 0));
+        return rc;
+    }
+    int lane = 0;  // pipelined: the next lane's workspace and stream
+    if (c->nlanes > 1) lane = (int)(c->next_lane++ % (unsigned)c->nlanes);
+    return enqueue_encode(c, f->d_rgb, f->frame_stride, f->sample_bytes, f->n_frames, g, opt, f->d_out, f->out_stride,
+                          f->d_out_len, c->lanes[lane]->stream, lane, true, nullptr, sf);
+}
+
 extern "C" int dmmt_encode_device(dmmt_ctx* c, const dmmt_device_frames* f, const dmmt_options* opt, void* stream) {
     c = primary(c);
     if (!c || !f) return DMMT_E_INVALID_ARGUMENT;
@@ -711,24 +745,46 @@ extern "C" int dmmt_encode_device(dmmt_ctx* c, const dmmt_device_frames* f, cons
     Geom g;
     if ((rc = make_checked_geom(f->width, f->height, opt->subsampling, f->maxval, opt->restart_interval, &g))) return rc;
     if (f->out_stride < max_jpeg_bytes(g)) return DMMT_E_CAPACITY;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if ((rc = set_device(c))) return rc;
-    if (stream) {
-        // the caller's stream runs on lane 0's workspace: it waits for the work
-        // already queued on lane 0, and lane 0 for this call, in both directions
-        hipStream_t st = (hipStream_t)stream;
-        HIP_TRY(hipEventRecord(c->ev_lane0, c->stream));
-        HIP_TRY(hipStreamWaitEvent(st, c->ev_lane0, 0));
-        rc = enqueue_encode(c, f->d_rgb, f->frame_stride, f->sample_bytes, f->n_frames, g, opt, f->d_out,
-                            f->out_stride, f->d_out_len, st, 0, true);
-        HIP_TRY(hipEventRecord(c->ev_caller, st));
-        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_caller, 0));
-        return rc;
-    }
-    int lane = 0;  // pipelined: the next lane's workspace and stream
-    if (c->nlanes > 1) lane = (int)(c->next_lane++ % (unsigned)c->nlanes);
-    return enqueue_encode(c, f->d_rgb, f->frame_stride, f->sample_bytes, f->n_frames, g, opt, f->d_out, f->out_stride,
-                          f->d_out_len, c->lanes[lane]->stream, lane, true);
+    return encode_device_frames(c, f, opt, stream, g, nullptr);
+}
+
+extern "C" size_t dmmt_surface_span(const dmmt_device_surfaces* s) {
+    if (!s || !s->width || !s->height) return 0;
+    const int spp = surface_samples_per_pixel(s->format, s->sample_bytes);
+    if (!spp) return 0;
+    return (size_t)(s->height - 1) * s->row_pitch + (size_t)s->width * spp * s->sample_bytes;
+}
+
+extern "C" int dmmt_encode_device_surfaces(dmmt_ctx* c, const dmmt_device_surfaces* s, const dmmt_options* opt,
+                                           void* stream) {
+    c = primary(c);
+    if (!c || !s) return DMMT_E_INVALID_ARGUMENT;
+    int rc;
+    if ((rc = validate(opt))) return rc;
+    if (s->n_frames <= 0 || !s->d_out || !s->d_out_len) return DMMT_E_INVALID_ARGUMENT;
+    const int spp = surface_samples_per_pixel(s->format, s->sample_bytes);  // 0: outside the supported matrix
+    if (!spp) return DMMT_E_INVALID_ARGUMENT;
+    const size_t sb = s->sample_bytes;
+    const int nplanes = s->format == DMMT_PF_PLANAR ? 3 : 1;
+    for (int p = 0; p < nplanes; ++p)
+        if (!s->d_plane[p] || (uintptr_t)s->d_plane[p] % sb) return DMMT_E_INVALID_ARGUMENT;
+    if (s->row_pitch < (size_t)s->width * spp * sb || s->row_pitch % sb || s->row_pitch > DMMT_MAX_ROW_PITCH ||
+        s->frame_stride % sb)
+        return DMMT_E_INVALID_ARGUMENT;
+    Geom g;
+    if ((rc = make_checked_geom(s->width, s->height, opt->subsampling, s->maxval, opt->restart_interval, &g))) return rc;
+    if (s->out_stride < max_jpeg_bytes(g)) return DMMT_E_CAPACITY;
+    Surface sf{};
+    for (int p = 0; p < nplanes; ++p) sf.plane[p] = s->d_plane[p];
+    sf.row_pitch = s->row_pitch;
+    sf.format = s->format;
+    dmmt_device_frames f{};
+    f.d_rgb = s->d_plane[0];
+    f.frame_stride = s->frame_stride;
+    f.n_frames = s->n_frames;
+    f.width = s->width, f.height = s->height, f.maxval = s->maxval, f.sample_bytes = s->sample_bytes;
+    f.d_out = s->d_out, f.out_stride = s->out_stride, f.d_out_len = s->d_out_len;
+    return encode_device_frames(c, &f, opt, stream, g, &sf);
 }
 
 // Host-memory batch of equal-geometry images -> host JPEGs.

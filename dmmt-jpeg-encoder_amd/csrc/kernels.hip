@@ -31,6 +31,7 @@
 #include "device_common.hpp"
 #include "jpeg_common.hpp"
 #include "kernels.hpp"
+#include "surface_load.hpp"
 #include "wave_merge.hpp"
 
 namespace dmmt {
@@ -282,6 +283,96 @@ struct RawTile {
     }
 };
 
+// Raw pixel staging of a surface (dmmt_device_surfaces): rows row_pitch bytes
+// apart, 3 or 4 interleaved samples per pixel or three planes of one sample each.
+// As RawTile, with the chunk arithmetic of surface_load.hpp: a pixel row stages as
+// NPL tile rows (one per plane, tile row ly * NPL + p), each with the misalignment
+// of its own first byte; nothing outside [plane, plane + span) is read, and every
+// byte past the rectangle's right edge or bottom stages as 0.
+enum { LAY_TIGHT = 0, LAY_RGB = 1, LAY_RGBX = 2, LAY_PLANAR = 3 };
+template <int LAY>
+struct SurfLayout {
+    static constexpr int NPL = LAY == LAY_PLANAR ? 3 : 1;                        // planes
+    static constexpr int SPP = LAY == LAY_RGBX ? 4 : (LAY == LAY_PLANAR ? 1 : 3);  // samples per pixel of a plane
+};
+struct SurfMem {
+    const uint8_t* base;
+    __device__ __forceinline__ void load16(long long off, uint32_t (&w)[4]) const {
+        const uint4 v = ld16_nt(base + off);
+        w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
+    }
+    __device__ __forceinline__ uint32_t load1(long long off) const { return base[off]; }
+};
+template <typename Sample, int ROWS, int LAY>
+struct SurfTile {
+    static constexpr int NPL = SurfLayout<LAY>::NPL;
+    static constexpr int BPP = SurfLayout<LAY>::SPP * (int)sizeof(Sample);  // bytes per pixel of a plane
+    static constexpr int RB = 256 * BPP;
+    static constexpr int RC = RB / 16 + 1;
+    static constexpr int RS = RC * 16;
+    static constexpr int NCHUNK = ROWS * NPL * RC;
+    static constexpr int NQ = (NCHUNK + 255) / 256;
+    static constexpr int BYTES = NCHUNK * 16;
+
+    // plane p's first byte of the frame (the three pointers as values: an indexed
+    // read of the kernel argument would put it into scratch)
+    struct Planes {
+        const uint8_t *p0, *p1, *p2;
+    };
+    __device__ static __forceinline__ Planes planes(const SurfArgs& sa, size_t foff) {
+        return Planes{sa.plane[0] + foff, sa.plane[NPL == 1 ? 0 : 1] + foff, sa.plane[NPL == 1 ? 0 : 2] + foff};
+    }
+    __device__ static __forceinline__ const uint8_t* plane(const Planes& pl, int p) {
+        return NPL == 1 || p == 0 ? pl.p0 : (p == 1 ? pl.p1 : pl.p2);
+    }
+    __device__ static __forceinline__ int misalign32(const uint8_t* pbase, const SurfArgs& sa, int x0, int py) {
+        return surf_misalign32((uint32_t)(uintptr_t)pbase, (uint32_t)sa.pitch, BPP, x0, py);
+    }
+
+    __device__ static __forceinline__ void load(const SurfArgs& sa, size_t foff, const Geom& g, int x0, int y0, int tid,
+                                                uint4 (&v)[NQ]) {
+        // interior tile (wave-uniform), as RawTile::load: the same offsets in every plane
+        const Planes pl = planes(sa, foff);
+        const long long first = surf_row_start(sa.pitch, BPP, x0, y0);
+        if (x0 + 256 <= g.width && y0 + ROWS <= g.height &&
+            surf_interior(first, surf_row_start(sa.pitch, BPP, x0, y0 + ROWS - 1), RB, sa.span)) {
+#pragma unroll
+            for (int i = 0; i < NQ; ++i) {
+                const int q = tid + 256 * i;
+                const int tr = q / RC, j = q - (q / RC) * RC;
+                const int row = tr / NPL, p = tr - (tr / NPL) * NPL;
+                const uint8_t* pb = plane(pl, p);
+                const long long c = surf_interior_chunk((uint32_t)(uintptr_t)pb, first + (long long)row * sa.pitch, j);
+                v[i] = q < NCHUNK ? ld16_nt(pb + c) : make_uint4(0u, 0u, 0u, 0u);
+            }
+            return;
+        }
+        const long long rowbytes = surf_row_bytes(g.width, BPP, x0);
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) {
+            v[i] = make_uint4(0u, 0u, 0u, 0u);
+            const int q = tid + 256 * i;
+            const int tr = q / RC, j = q - (q / RC) * RC;
+            const int row = tr / NPL, p = tr - (tr / NPL) * NPL;
+            const int py = y0 + row;
+            if (q >= NCHUNK || py >= g.height) continue;
+            const SurfMem m{plane(pl, p)};
+            uint32_t w[4];
+            surf_load_chunk(m, surf_row_start(sa.pitch, BPP, x0, py), misalign32(m.base, sa, x0, py), rowbytes, sa.span,
+                            j, w);
+            v[i] = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+    }
+
+    __device__ static __forceinline__ void stage(uint8_t* sRaw, int tid, const uint4 (&v)[NQ]) {
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) {
+            const int q = tid + 256 * i;
+            if (q < NCHUNK) reinterpret_cast<uint4*>(sRaw)[q] = v[i];
+        }
+    }
+};
+
 // One workgroup (256 threads) per tile = TM horizontally adjacent MCUs of one
 // MCU row (256 padded pixel columns, 8*VR rows), looping over the frame's tiles
 // (grid = resident workgroups; blockIdx.y = frame) with the next tile's pixels
@@ -300,11 +391,16 @@ struct RawTile {
 //     cost here, spread over the block's 8 lanes.
 // Two barriers per tile: the next tile's staging barrier also keeps its phase A
 // from overwriting sT before every wave has read its columns.
-template <int HR, int VR, typename Sample, int WPE>
-__global__ __launch_bounds__(256, WPE) void k_front(const Sample* __restrict__ rgb, size_t frame_stride, Geom g,
-                                               const float* __restrict__ norm_lut,
-                                               const float* __restrict__ qtab,  // [2][64] natural, as f32
-                                               int16_t* __restrict__ coef, int* __restrict__ status) {
+// LAY: the input layout.  LAY_TIGHT (k_front) reads rgb + frame * frame_stride
+// samples through RawTile; the others (k_front_surf) read the surface sa, its
+// frames frame_stride bytes apart, through SurfTile, and phase A picks its three
+// samples at SPP-sample pixels of NPL planes (sa.bgr, wave-uniform: samples 0 and
+// 2 of an interleaved pixel change roles).
+template <int HR, int VR, typename Sample, int LAY>
+__device__ __forceinline__ void front_body(const Sample* __restrict__ rgb, size_t frame_stride, const SurfArgs& sa,
+                                           Geom g, const float* __restrict__ norm_lut,
+                                           const float* __restrict__ qtab,  // [2][64] natural, as f32
+                                           int16_t* __restrict__ coef, int* __restrict__ status) {
     constexpr int TM = 32 / HR;      // MCUs per tile
     constexpr int ROWS = 8 * VR;     // pixel rows per tile
     constexpr int NLUMA = HR * VR;
@@ -324,11 +420,13 @@ __global__ __launch_bounds__(256, WPE) void k_front(const Sample* __restrict__ r
     constexpr int NJ = 8 * CB * SP;  // fused jobs (chroma row, chroma block, luma block column): 256
     constexpr int NCS = 8 / SP;      // chroma samples of a job
     constexpr int SB = (int)sizeof(Sample);
-    constexpr int PXB = 8 * 3 * SB;  // raw bytes of one job row (8 pixels)
+    constexpr int NPL = SurfLayout<LAY>::NPL;
+    constexpr int SPP = SurfLayout<LAY>::SPP;
+    constexpr int PXB = 8 * SPP * SB;  // raw bytes of one job row (8 pixels) in a plane
     constexpr int PXW = PXB / 4;
     constexpr int NCJ = NB * 8;      // column jobs
     constexpr int JPT = (NCJ + 255) / 256;
-    using Raw = RawTile<Sample, ROWS>;
+    using Raw = std::conditional_t<LAY == LAY_TIGHT, RawTile<Sample, ROWS>, SurfTile<Sample, ROWS, LAY>>;
 
     // row-transformed blocks (A -> C)
     __shared__ __attribute__((aligned(16))) float sT[NB * BS + 4];
@@ -340,8 +438,16 @@ __global__ __launch_bounds__(256, WPE) void k_front(const Sample* __restrict__ r
     DMMT_TRACE_START;
     const int tid = threadIdx.x;
     const int frame = blockIdx.y;
-    const uint8_t* fbase = reinterpret_cast<const uint8_t*>(rgb + (size_t)frame * frame_stride);
-    const long long fbytes = (long long)g.width * g.height * 3 * SB;
+    // tight frames: frame_stride in samples from rgb; surfaces: in bytes, the same offset in every plane
+    const uint8_t* fbase = nullptr;
+    long long fbytes = 0;
+    size_t foff = 0;
+    if constexpr (LAY == LAY_TIGHT) {
+        fbase = reinterpret_cast<const uint8_t*>(rgb + (size_t)frame * frame_stride);
+        fbytes = (long long)g.width * g.height * 3 * SB;
+    } else {
+        foff = (size_t)frame * frame_stride;
+    }
     if (tid < 128) sQ[tid] = qtab[tid];
     if (tid < 128) sRQ[tid] = SB == 4 ? 1.0f / qtab[tid] : c_arai_scale[(tid >> 3) & 7] * (1.0f / qtab[tid]);
     if (SB == 1) sLut[tid] = norm_lut[tid];
@@ -353,9 +459,15 @@ __global__ __launch_bounds__(256, WPE) void k_front(const Sample* __restrict__ r
     const bool check_range = SB != 4 && g.maxval < (SB == 1 ? 255 : 65535);
 
     uint4 raw[Raw::NQ];
+    auto load_tile = [&](int tx0, int ty0) {
+        if constexpr (LAY == LAY_TIGHT)
+            Raw::load(fbase, fbytes, g, tx0, ty0, tid, raw);
+        else
+            Raw::load(sa, foff, g, tx0, ty0, tid, raw);
+    };
     if ((int)blockIdx.x < ntiles) {
         const int my = blockIdx.x / tiles_per_row;
-        Raw::load(fbase, fbytes, g, (blockIdx.x - my * tiles_per_row) * TM * 8 * HR, my * ROWS, tid, raw);
+        load_tile((blockIdx.x - my * tiles_per_row) * TM * 8 * HR, my * ROWS);
     }
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int my = tile / tiles_per_row;
@@ -369,7 +481,7 @@ __global__ __launch_bounds__(256, WPE) void k_front(const Sample* __restrict__ r
             const int nt = tile + gridDim.x;
             if (nt < ntiles) {
                 const int ny = nt / tiles_per_row;
-                Raw::load(fbase, fbytes, g, (nt - ny * tiles_per_row) * TM * 8 * HR, ny * ROWS, tid, raw);
+                load_tile((nt - ny * tiles_per_row) * TM * 8 * HR, ny * ROWS);
             }
         }
 
@@ -382,28 +494,35 @@ __global__ __launch_bounds__(256, WPE) void k_front(const Sample* __restrict__ r
             const int h = tid % SP, job = tid / SP;
             const int c = job % CB, r = job / CB;  // chroma block, chroma row
             const int lx0 = c * 8 * HR + 8 * h;    // first pixel column of the job
-            uint32_t pw[VR][SB == 4 ? 1 : PXW];    // raw bytes of the job's VR pixel rows (integer samples)
-            const float* fsrc[VR];                 // the rows themselves (float samples)
+            uint32_t pw[VR * NPL][SB == 4 ? 1 : PXW];  // raw bytes of the job's VR pixel rows (integer samples)
+            const float* fsrc[VR * NPL];               // the rows themselves (float samples)
 #pragma unroll
             for (int dy = 0; dy < VR; ++dy) {
-                const int ly = r * VR + dy;
-                const int mis = Raw::misalign32(fbase, g, x0, y0 + ly);
-                const uint8_t* src = sRaw + ly * Raw::RS + mis + lx0 * 3 * SB;
-                fsrc[dy] = reinterpret_cast<const float*>(src);
-                if constexpr (SB == 4) {
-                    pw[dy][0] = 0u;
-                } else if ((mis & 7) == 0) {
 #pragma unroll
-                    for (int k = 0; k < PXW / 2; ++k) {
-                        const uint2 u = reinterpret_cast<const uint2*>(src)[k];
-                        pw[dy][2 * k] = u.x;
-                        pw[dy][2 * k + 1] = u.y;
+                for (int p = 0; p < NPL; ++p) {
+                    const int ly = r * VR + dy;
+                    int mis;
+                    if constexpr (LAY == LAY_TIGHT)
+                        mis = Raw::misalign32(fbase, g, x0, y0 + ly);
+                    else
+                        mis = Raw::misalign32(sa.plane[p] + foff, sa, x0, y0 + ly);
+                    const uint8_t* src = sRaw + (ly * NPL + p) * Raw::RS + mis + lx0 * SPP * SB;
+                    fsrc[dy * NPL + p] = reinterpret_cast<const float*>(src);
+                    if constexpr (SB == 4) {
+                        pw[dy * NPL + p][0] = 0u;
+                    } else if ((mis & 7) == 0) {
+#pragma unroll
+                        for (int k = 0; k < PXW / 2; ++k) {
+                            const uint2 u = reinterpret_cast<const uint2*>(src)[k];
+                            pw[dy * NPL + p][2 * k] = u.x;
+                            pw[dy * NPL + p][2 * k + 1] = u.y;
+                        }
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < PXW; ++k)
+                            pw[dy * NPL + p][k] = (uint32_t)src[4 * k] | ((uint32_t)src[4 * k + 1] << 8) |
+                                                  ((uint32_t)src[4 * k + 2] << 16) | ((uint32_t)src[4 * k + 3] << 24);
                     }
-                } else {
-#pragma unroll
-                    for (int k = 0; k < PXW; ++k)
-                        pw[dy][k] = (uint32_t)src[4 * k] | ((uint32_t)src[4 * k + 1] << 8) |
-                                    ((uint32_t)src[4 * k + 2] << 16) | ((uint32_t)src[4 * k + 3] << 24);
                 }
             }
             float yv[VR][8];
@@ -419,16 +538,33 @@ __global__ __launch_bounds__(256, WPE) void k_front(const Sample* __restrict__ r
                         const int jx = k * HR + dx;  // pixel within the job row
                         float rr, gg, bb;
                         if constexpr (SB == 4) {  // Image<f32> dots as given (0.0 past the edges)
-                            rr = fsrc[dy][jx * 3];
-                            gg = fsrc[dy][jx * 3 + 1];
-                            bb = fsrc[dy][jx * 3 + 2];
+                            if constexpr (LAY == LAY_PLANAR) {
+                                rr = fsrc[dy * NPL][jx];
+                                gg = fsrc[dy * NPL + 1][jx];
+                                bb = fsrc[dy * NPL + 2][jx];
+                            } else {
+                                rr = fsrc[dy][jx * SPP];
+                                gg = fsrc[dy][jx * SPP + 1];
+                                bb = fsrc[dy][jx * SPP + 2];
+                                if constexpr (LAY != LAY_TIGHT) {
+                                    const float s0 = rr;
+                                    rr = sa.bgr ? bb : rr;
+                                    bb = sa.bgr ? s0 : bb;
+                                }
+                            }
                         } else {
                             uint32_t sv[3];
 #pragma unroll
                             for (int ch = 0; ch < 3; ++ch) {
-                                const int si = jx * 3 + ch;  // sample index in the row
-                                sv[ch] = SB == 1 ? (pw[dy][si >> 2] >> (8 * (si & 3))) & 0xFFu
-                                                 : (pw[dy][si >> 1] >> (16 * (si & 1))) & 0xFFFFu;
+                                const int si = LAY == LAY_PLANAR ? jx : jx * SPP + ch;  // sample index in the row
+                                const uint32_t* rw = pw[LAY == LAY_PLANAR ? dy * NPL + ch : dy];
+                                sv[ch] = SB == 1 ? (rw[si >> 2] >> (8 * (si & 3))) & 0xFFu
+                                                 : (rw[si >> 1] >> (16 * (si & 1))) & 0xFFFFu;
+                            }
+                            if constexpr (LAY == LAY_RGB || LAY == LAY_RGBX) {  // B,G,R[,x]: two selects per pixel
+                                const uint32_t s0 = sv[0];
+                                sv[0] = sa.bgr ? sv[2] : sv[0];
+                                sv[2] = sa.bgr ? s0 : sv[2];
                             }
                             if constexpr (CHECK) smax = max(smax, max(sv[0], max(sv[1], sv[2])));
                             if (SB == 1) {
@@ -555,6 +691,23 @@ __global__ __launch_bounds__(256, WPE) void k_front(const Sample* __restrict__ r
     if (bad) raise_status(status, bad);  // 1: sample above maxval
     DMMT_TRACE(5);
     DMMT_TRACE_FLUSH(0, 0);
+}
+
+template <int HR, int VR, typename Sample, int WPE>
+__global__ __launch_bounds__(256, WPE) void k_front(const Sample* __restrict__ rgb, size_t frame_stride, Geom g,
+                                               const float* __restrict__ norm_lut,
+                                               const float* __restrict__ qtab,  // [2][64] natural, as f32
+                                               int16_t* __restrict__ coef, int* __restrict__ status) {
+    front_body<HR, VR, Sample, LAY_TIGHT>(rgb, frame_stride, SurfArgs{}, g, norm_lut, qtab, coef, status);
+}
+
+// the same tile loop over a surface (frame_stride in bytes)
+template <int HR, int VR, typename Sample, int LAY, int WPE>
+__global__ __launch_bounds__(256, WPE) void k_front_surf(SurfArgs sa, size_t frame_stride, Geom g,
+                                                    const float* __restrict__ norm_lut,
+                                                    const float* __restrict__ qtab, int16_t* __restrict__ coef,
+                                                    int* __restrict__ status) {
+    front_body<HR, VR, Sample, LAY>(nullptr, frame_stride, sa, g, norm_lut, qtab, coef, status);
 }
 
 // ============================================================== k_hist
@@ -1483,34 +1636,97 @@ constexpr int front_wpe() {
     return sizeof(S) == 1 ? (HR * VR == 4 ? FRONT_WPE_420 : 4) : 1;
 }
 
+// The resident workgroups of one k_front instantiation: one workgroup per
+// resident slot, each looping over tiles and prefetching the next.  A launcher
+// keeps one as a function static, computed once (thread-safe initialisation).
+struct FrontCfg {
+    int resident, n_cus;
+    bool per_cu_env;
+};
+template <typename K>
+static FrontCfg front_cfg(K kernel) {
+    int per_cu = 0, dev = 0, cus = 0;
+    bool env = false;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || per_cu < 1) per_cu = 2;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
+        cus = 256;
+    if (const char* e = getenv("DMMT_FRONT_PER_CU")) {  // tuning knob (both lane modes)
+        per_cu = atoi(e) > 0 ? atoi(e) : per_cu;
+        env = true;
+    }
+    return FrontCfg{per_cu * cus, cus, env};
+}
+// per_cu_cap: fewer resident workgroups per CU (a context of several lanes)
+static dim3 front_grid(const FrontCfg& cfg, long long ntiles, int n_frames, int per_cu_cap) {
+    const int res = per_cu_cap > 0 && !cfg.per_cu_env ? std::min(cfg.resident, per_cu_cap * cfg.n_cus) : cfg.resident;
+    return dim3(clampi(ntiles, 1, res / n_frames > 0 ? res / n_frames : 1), n_frames);
+}
+
 template <int HR, int VR, typename S>
 static void front_impl(const void* rgb, size_t stride_elems, int n_frames, const Geom& g, const Work& w,
                        hipStream_t st, int per_cu_cap) {
     constexpr int TM = 32 / HR;
     const long long ntiles = (long long)((g.mcux + TM - 1) / TM) * g.mcuy;
-    // one workgroup per resident slot: each loops over tiles, prefetching the next
-    static int resident = 0, n_cus = 0;
-    static bool per_cu_env = false;
-    if (!resident) {
-        int per_cu = 0, dev = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_front<HR, VR, S, front_wpe<HR, VR, S>()>, 256, 0) != hipSuccess ||
-            per_cu < 1)
-            per_cu = 2;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-            cus = 256;
-        if (const char* e = getenv("DMMT_FRONT_PER_CU")) {  // tuning knob (both lane modes)
-            per_cu = atoi(e) > 0 ? atoi(e) : per_cu;
-            per_cu_env = true;
-        }
-        resident = per_cu * cus;
-        n_cus = cus;
-    }
-    // per_cu_cap: fewer resident workgroups per CU (a context of several lanes)
-    const int res = per_cu_cap > 0 && !per_cu_env ? std::min(resident, per_cu_cap * n_cus) : resident;
-    dim3 grid(clampi(ntiles, 1, res / n_frames > 0 ? res / n_frames : 1), n_frames);
-    hipLaunchKernelGGL((k_front<HR, VR, S, front_wpe<HR, VR, S>()>), grid, dim3(256), 0, st, (const S*)rgb, stride_elems, g, w.norm_lut,
+    static const FrontCfg cfg = [] { return front_cfg(k_front<HR, VR, S, front_wpe<HR, VR, S>()>); }();
+    hipLaunchKernelGGL((k_front<HR, VR, S, front_wpe<HR, VR, S>()>), front_grid(cfg, ntiles, n_frames, per_cu_cap),
+                       dim3(256), 0, st, (const S*)rgb, stride_elems, g, w.norm_lut, w.qtab, w.coef, w.status);
+}
+
+template <int HR, int VR, typename S, int LAY>
+static void front_surf_impl(const SurfArgs& sa, size_t frame_stride, int n_frames, const Geom& g, const Work& w,
+                            hipStream_t st, int per_cu_cap) {
+    constexpr int TM = 32 / HR;
+    const long long ntiles = (long long)((g.mcux + TM - 1) / TM) * g.mcuy;
+    static const FrontCfg cfg = [] { return front_cfg(k_front_surf<HR, VR, S, LAY, front_wpe<HR, VR, S>()>); }();
+    hipLaunchKernelGGL((k_front_surf<HR, VR, S, LAY, front_wpe<HR, VR, S>()>),
+                       front_grid(cfg, ntiles, n_frames, per_cu_cap), dim3(256), 0, st, sa, frame_stride, g, w.norm_lut,
                        w.qtab, w.coef, w.status);
+}
+template <typename S, int LAY>
+static void front_surf_sub(const SurfArgs& sa, size_t frame_stride, int n_frames, const Geom& g, const Work& w,
+                           hipStream_t st, int per_cu_cap) {
+    if (g.hr == 1)
+        front_surf_impl<1, 1, S, LAY>(sa, frame_stride, n_frames, g, w, st, per_cu_cap);
+    else if (g.vr == 1)
+        front_surf_impl<2, 1, S, LAY>(sa, frame_stride, n_frames, g, w, st, per_cu_cap);
+    else
+        front_surf_impl<2, 2, S, LAY>(sa, frame_stride, n_frames, g, w, st, per_cu_cap);
+}
+
+// samples per pixel of a plane, 0: a (format, sample_bytes) pair outside the supported matrix
+int surface_samples_per_pixel(int format, int sample_bytes) {
+    const bool sb_ok = sample_bytes == 1 || sample_bytes == 2 || sample_bytes == 4;
+    if (format == SURF_RGB || format == SURF_BGR) return sb_ok ? 3 : 0;
+    if (format == SURF_RGBX || format == SURF_BGRX) return sample_bytes == 1 ? 4 : 0;
+    if (format == SURF_PLANAR) return sample_bytes == 1 || sample_bytes == 4 ? 1 : 0;
+    return 0;
+}
+
+hipError_t launch_front_surface(const Surface& sf, size_t frame_stride_bytes, int sample_bytes, int n_frames,
+                                const Geom& g, const Work& w, hipStream_t st, int per_cu_cap) {
+    const int spp = surface_samples_per_pixel(sf.format, sample_bytes);
+    if (!spp) return hipErrorInvalidValue;
+    SurfArgs sa{};
+    for (int p = 0; p < 3; ++p) sa.plane[p] = (const uint8_t*)sf.plane[p];
+    sa.pitch = (long long)sf.row_pitch;
+    sa.span = (long long)(g.height - 1) * sa.pitch + (long long)g.width * spp * sample_bytes;
+    sa.bgr = sf.format == SURF_BGR || sf.format == SURF_BGRX;
+    if (sf.format == SURF_PLANAR) {
+        if (sample_bytes == 1)
+            front_surf_sub<uint8_t, LAY_PLANAR>(sa, frame_stride_bytes, n_frames, g, w, st, per_cu_cap);
+        else
+            front_surf_sub<float, LAY_PLANAR>(sa, frame_stride_bytes, n_frames, g, w, st, per_cu_cap);
+    } else if (spp == 4) {
+        front_surf_sub<uint8_t, LAY_RGBX>(sa, frame_stride_bytes, n_frames, g, w, st, per_cu_cap);
+    } else if (sample_bytes == 1) {
+        front_surf_sub<uint8_t, LAY_RGB>(sa, frame_stride_bytes, n_frames, g, w, st, per_cu_cap);
+    } else if (sample_bytes == 2) {
+        front_surf_sub<uint16_t, LAY_RGB>(sa, frame_stride_bytes, n_frames, g, w, st, per_cu_cap);
+    } else {
+        front_surf_sub<float, LAY_RGB>(sa, frame_stride_bytes, n_frames, g, w, st, per_cu_cap);
+    }
+    return hipGetLastError();
 }
 
 hipError_t launch_front(const void* rgb, size_t frame_stride_bytes, int sample_bytes, int n_frames, const Geom& g,

@@ -33,6 +33,26 @@ struct Work {
 
 enum Stage { ST_FRONT = 0, ST_HIST, ST_TABLES, ST_EMIT, ST_OFFSETS, ST_STUFFWRITE, ST_COUNT };
 
+// A device surface (dmmt_device_surfaces): format as dmmt_pixel_format
+enum { SURF_RGB = 0, SURF_BGR = 1, SURF_RGBX = 2, SURF_BGRX = 3, SURF_PLANAR = 4 };
+struct Surface {
+    const void* plane[3];  // interleaved: plane[0] only
+    size_t row_pitch;      // bytes between rows of a plane
+    int format;
+};
+// k_front_surf's view of it
+struct SurfArgs {
+    const uint8_t* plane[3];
+    long long pitch;  // bytes between rows
+    long long span;   // readable bytes of a plane, per frame (dmmt_surface_span)
+    int bgr;          // interleaved: samples 0 and 2 are B and R
+};
+// samples per pixel of a plane; 0: the (format, sample_bytes) pair is not supported
+int surface_samples_per_pixel(int format, int sample_bytes);
+// k_front over a surface (frames frame_stride_bytes apart in every plane)
+hipError_t launch_front_surface(const Surface& sf, size_t frame_stride_bytes, int sample_bytes, int n_frames,
+                                const Geom& g, const Work& w, hipStream_t st, int per_cu_cap = 0);
+
 // per_cu_cap: at most this many resident k_front workgroups per CU (0: as many as
 // fit, 4); a context of several lanes passes DMMT_FRONT_PER_CU_LANES
 hipError_t launch_front(const void* rgb, size_t frame_stride_bytes, int sample_bytes, int n_frames, const Geom& g,

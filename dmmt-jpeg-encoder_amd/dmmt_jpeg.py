@@ -85,6 +85,9 @@ def lib():
     L.dmmt_jpeg_encode.argtypes = [vp, P(DmmtImage), P(DmmtOptions), P(vp), P(sz)]
     L.dmmt_jpeg_encode_batch.argtypes = [vp, P(DmmtImage), ctypes.c_int, P(DmmtOptions), P(vp), P(sz)]
     L.dmmt_encode_device.argtypes = [vp, P(DmmtDeviceFrames), P(DmmtOptions), vp]
+    L.dmmt_encode_device_surfaces.argtypes = [vp, P(DmmtDeviceSurfaces), P(DmmtOptions), vp]
+    L.dmmt_surface_span.argtypes = [P(DmmtDeviceSurfaces)]
+    L.dmmt_surface_span.restype = sz
     L.dmmt_ctx_set_lanes.argtypes = [vp, ctypes.c_int]
     L.dmmt_max_jpeg_bytes.argtypes = [u16, u16, i32]
     L.dmmt_max_jpeg_bytes.restype = sz
@@ -166,6 +169,32 @@ class DmmtDeviceFrames(ctypes.Structure):
                 ("width", ctypes.c_uint16), ("height", ctypes.c_uint16), ("maxval", ctypes.c_uint16),
                 ("sample_bytes", ctypes.c_uint16), ("d_out", ctypes.c_void_p), ("out_stride", ctypes.c_size_t),
                 ("d_out_len", ctypes.c_void_p)]
+
+
+class DmmtDeviceSurfaces(ctypes.Structure):
+    _fields_ = [("d_plane", ctypes.c_void_p * 3), ("row_pitch", ctypes.c_size_t), ("frame_stride", ctypes.c_size_t),
+                ("n_frames", ctypes.c_int32), ("format", ctypes.c_int32),
+                ("width", ctypes.c_uint16), ("height", ctypes.c_uint16), ("maxval", ctypes.c_uint16),
+                ("sample_bytes", ctypes.c_uint16), ("d_out", ctypes.c_void_p), ("out_stride", ctypes.c_size_t),
+                ("d_out_len", ctypes.c_void_p)]
+
+
+class PixelFormat(enum.IntEnum):
+    """dmmt_pixel_format: the layout of a device surface"""
+    RGB = 0
+    BGR = 1
+    RGBX = 2
+    BGRX = 3
+    PLANAR = 4
+
+    def samples_per_pixel(self) -> int:
+        """samples per pixel of one plane"""
+        return {0: 3, 1: 3, 2: 4, 3: 4, 4: 1}[int(self)]
+
+
+def surface_span(s: DmmtDeviceSurfaces) -> int:
+    """dmmt_surface_span: the bytes of a plane the encoder may read, per frame"""
+    return int(lib().dmmt_surface_span(ctypes.byref(s)))
 
 
 class DmmtStripe(ctypes.Structure):
@@ -494,6 +523,140 @@ class Encoder:
         f.d_out, f.out_stride, f.d_out_len = d_out, out_stride, d_out_len
         opt = opt_c if opt_c is not None else options.to_c()
         _check(lib().dmmt_encode_device(self._ctx, ctypes.byref(f), ctypes.byref(opt), stream), "encode_device")
+
+    def encode_device_surfaces(self, d_planes, fmt: int, row_pitch: int, n_frames: int, width: int, height: int,
+                               options: JpegTransformationOptions, d_out: int, out_stride: int, d_out_len: int,
+                               frame_stride: int = 0, maxval: int = 255, sample_bytes: int = 1,
+                               stream: int | None = None, opt_c: DmmtOptions | None = None):
+        """dmmt_encode_device_surfaces: d_planes is one device pointer (interleaved
+        formats) or three (PixelFormat.PLANAR: R, G, B); enqueued, see synchronize()"""
+        s = self.surfaces(d_planes, fmt, row_pitch, n_frames, width, height, d_out, out_stride, d_out_len,
+                          frame_stride, maxval, sample_bytes)
+        opt = opt_c if opt_c is not None else options.to_c()
+        _check(lib().dmmt_encode_device_surfaces(self._ctx, ctypes.byref(s), ctypes.byref(opt), stream),
+               "encode_device_surfaces")
+
+    @staticmethod
+    def surfaces(d_planes, fmt: int, row_pitch: int, n_frames: int, width: int, height: int, d_out: int = 0,
+                 out_stride: int = 0, d_out_len: int = 0, frame_stride: int = 0, maxval: int = 255,
+                 sample_bytes: int = 1) -> DmmtDeviceSurfaces:
+        """fill a dmmt_device_surfaces struct (nothing is enqueued): d_planes is one
+        device pointer or the three of a planar surface"""
+        s = DmmtDeviceSurfaces()
+        planes = [d_planes] if isinstance(d_planes, int) else list(d_planes)
+        for i, ptr in enumerate(planes[:3]):
+            s.d_plane[i] = ptr
+        s.row_pitch, s.frame_stride, s.n_frames, s.format = row_pitch, frame_stride, n_frames, int(fmt)
+        s.width, s.height, s.maxval, s.sample_bytes = width, height, maxval, sample_bytes
+        s.d_out, s.out_stride, s.d_out_len = d_out, out_stride, d_out_len
+        return s
+
+    def _tensor_surface(self, t, layout, maxval):
+        """(planes, format, row_pitch, frame_stride, n_frames, width, height, maxval,
+        sample_bytes) of a tensor on this encoder's GPU, from its pointer and strides"""
+        if torch is None:
+            raise RuntimeError("encode_tensor needs torch")
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError("a torch tensor in device memory is required")
+        if t.device.index != self.device:
+            raise ValueError(f"the tensor is on {t.device}, the encoder on GPU {self.device}")
+        sizes = {torch.uint8: 1, torch.int16: 2, torch.float32: 4}
+        if hasattr(torch, "uint16"):
+            sizes[torch.uint16] = 2
+        if t.dtype not in sizes:
+            raise ValueError(f"dtype {t.dtype}: uint8, int16/uint16 or float32 samples are supported")
+        sb = sizes[t.dtype]
+        if t.dim() not in (3, 4):
+            raise ValueError("shape (H,W,3), (H,W,4) or (3,H,W), with an optional batch dimension, is required")
+        shape, stride = list(t.shape[-3:]), list(t.stride()[-3:])
+        if 0 in t.shape:
+            raise ValueError("an empty tensor")
+        name = (layout or "").upper()
+        bgr = name.endswith("-BGR")
+        if bgr:
+            name = name[:-4]
+        if not name:  # guessed only when the shape leaves no choice
+            hwc, chw = shape[2] in (3, 4), shape[0] == 3
+            if hwc == chw:
+                raise ValueError(f"shape {tuple(t.shape)} does not tell HWC from CHW: pass layout=")
+            name = "HWC" if hwc else "CHW"
+        if name == "HWC":
+            (h, w, c), (s_h, s_w, s_c) = shape, stride
+            if c not in (3, 4):
+                raise ValueError("HWC: 3 or 4 samples per pixel")
+            if c == 4 and sb != 1:
+                raise ValueError("4 samples per pixel: uint8 only")
+            if s_c != 1 or (w > 1 and s_w != c):
+                raise ValueError("HWC: the samples of a row must be contiguous (strides C along W, 1 along C)")
+            fmt = (PixelFormat.BGR if bgr else PixelFormat.RGB) if c == 3 else (PixelFormat.BGRX if bgr else PixelFormat.RGBX)
+            planes, row = [t.data_ptr()], w * c
+        elif name == "CHW":
+            (c, h, w), (s_c, s_h, s_w) = shape, stride
+            if c != 3:
+                raise ValueError("CHW: three planes")
+            if sb == 2:
+                raise ValueError("planar: uint8 or float32 samples")
+            if w > 1 and s_w != 1:
+                raise ValueError("CHW: the samples of a row must be contiguous (stride 1 along W)")
+            fmt = PixelFormat.PLANAR
+            planes = [t.data_ptr() + k * s_c * sb for k in ((2, 1, 0) if bgr else (0, 1, 2))]
+            row = w
+        else:
+            raise ValueError(f"layout {layout!r}: HWC, CHW, HWC-BGR or CHW-BGR")
+        pitch = s_h * sb if h > 1 else row * sb
+        if pitch < row * sb:
+            raise ValueError("rows overlap (a row stride below the row's samples)")
+        n = t.shape[0] if t.dim() == 4 else 1
+        fstride = t.stride()[0] * sb if t.dim() == 4 and n > 1 else 0
+        if w > 65535 or h > 65535:
+            raise ValueError("at most 65535 x 65535 pixels")
+        if maxval is None:
+            maxval = 255 if sb == 1 else 65535
+        return planes, fmt, pitch, fstride, n, w, h, int(maxval), sb
+
+    def encode_tensor_device(self, t, options: JpegTransformationOptions, *, layout: str | None = None,
+                             maxval: int | None = None):
+        """Encode a tensor where it lies: uint8, int16/uint16 or (normalised) float32,
+        shape (H,W,3), (H,W,4) or (3,H,W) with an optional batch dimension, any row,
+        plane and batch strides (a crop or slice of a larger tensor is fine), samples
+        contiguous along a row.  layout: "HWC" or "CHW" (guessed when the shape leaves
+        no choice), "-BGR" appended for B,G,R order.  No copy is made: a tensor that
+        does not fit raises ValueError.  Ordered on torch's current stream, nothing is
+        synchronised; returns (out, lens): uint8 [n, out_stride] and int32 [n] device
+        tensors, JPEG f = out[f, :lens[f]].  Errors the kernels find are raised by
+        synchronize()."""
+        planes, fmt, pitch, fstride, n, w, h, mv, sb = self._tensor_surface(t, layout, maxval)
+        cap = max_jpeg_bytes(w, h, int(options.chroma_subsampling_preset))
+        out = torch.empty((n, cap), dtype=torch.uint8, device=t.device)
+        lens = torch.empty((n,), dtype=torch.int32, device=t.device)
+        cur = torch.cuda.current_stream(t.device)
+        if cur.cuda_stream:
+            run = cur
+        else:
+            # the default stream has no handle to pass on (NULL means the context's
+            # lanes): run on a stream of our own, ordered after it and before it
+            if getattr(self, "_tensor_stream", None) is None:
+                self._tensor_stream = torch.cuda.Stream(t.device)
+            run = self._tensor_stream
+            run.wait_stream(cur)
+        self.encode_device_surfaces(planes if fmt == PixelFormat.PLANAR else planes[0], fmt, pitch, n, w, h, options,
+                                    out.data_ptr(), cap, lens.data_ptr(), frame_stride=fstride, maxval=mv,
+                                    sample_bytes=sb, stream=run.cuda_stream)
+        if run is not cur:
+            # t, out and lens belong to cur's allocator pool but are used on run: that
+            # is safe only because cur waits for run here, before it can reuse them
+            cur.wait_stream(run)
+        return out, lens
+
+    def encode_tensor(self, t, options: JpegTransformationOptions, *, layout: str | None = None,
+                      maxval: int | None = None):
+        """encode_tensor_device, one synchronize and a copy back: a list of bytes, one
+        JPEG per frame"""
+        out, lens = self.encode_tensor_device(t, options, layout=layout, maxval=maxval)
+        self.synchronize()
+        n = lens.cpu().tolist()
+        host = out.cpu().numpy()
+        return [host[i, :n[i]].tobytes() for i in range(len(n))]
 
     def set_lanes(self, n: int):
         """pipelined device encodes: consecutive encode_device calls with stream None

@@ -152,6 +152,46 @@ int dmmt_encode_device(dmmt_ctx* ctx, const dmmt_device_frames* frames, const dm
 int dmmt_ctx_set_lanes(dmmt_ctx* ctx, int n);
 size_t dmmt_max_jpeg_bytes(uint16_t width, uint16_t height, int32_t subsampling);
 
+/* ---- device surfaces (extension) ---------------------------------------------------------
+ * dmmt_encode_device for frames that do not lie tightly packed as R,G,B: a row pitch, B,G,R
+ * order, a 4th sample per pixel, or three planes.  The reference's Image<f32> is always
+ * packed R,G,B (image.rs:7-11); these layouts are what a renderer, a video decoder or a
+ * strided tensor leaves in HBM.  The bytes written are those of dmmt_encode_device for the
+ * same pixels repacked. */
+enum dmmt_pixel_format {
+    DMMT_PF_RGB = 0,         /* interleaved R,G,B            (3 samples per pixel) */
+    DMMT_PF_BGR = 1,         /* interleaved B,G,R                                  */
+    DMMT_PF_RGBX = 2,        /* interleaved R,G,B,x: the 4th sample is ignored     */
+    DMMT_PF_BGRX = 3,        /* interleaved B,G,R,x                                */
+    DMMT_PF_PLANAR = 4       /* three planes, one sample per pixel each            */
+};
+/* Supported: RGB and BGR with sample_bytes 1, 2 and 4; RGBX and BGRX with sample_bytes 1;
+ * PLANAR with sample_bytes 1 and 4 (any other pair: DMMT_E_INVALID_ARGUMENT).
+ * A region of interest: point d_plane[*] at the rectangle's first sample (any address that
+ * is a multiple of sample_bytes) and keep the parent's row_pitch.  Another channel order of
+ * planes is the order of the three pointers.
+ * For every plane p and frame f the library reads only bytes of
+ * [d_plane[p] + f * frame_stride, ... + dmmt_surface_span(s)); of those, only the
+ * rectangle's used samples influence the output or the maxval check. */
+#define DMMT_MAX_ROW_PITCH ((size_t)1 << 30) /* largest row_pitch accepted */
+typedef struct dmmt_device_surfaces {
+    const void* d_plane[3];  /* interleaved: d_plane[0] only; planar: the R, G, B planes */
+    size_t row_pitch;        /* bytes between rows of a plane; >= the row's own bytes, a multiple of
+                                sample_bytes, <= DMMT_MAX_ROW_PITCH */
+    size_t frame_stride;     /* bytes between frames (the same for every plane), a multiple of sample_bytes */
+    int32_t n_frames;
+    int32_t format;          /* dmmt_pixel_format */
+    uint16_t width, height, maxval, sample_bytes;  /* as dmmt_image: the rectangle that is encoded */
+    uint8_t* d_out; size_t out_stride; uint32_t* d_out_len;   /* as dmmt_device_frames */
+} dmmt_device_surfaces;
+/* Stream, lanes and errors as dmmt_encode_device (NULL stream: round-robin over the lanes;
+ * errors through dmmt_ctx_synchronize; a multi-GPU context: member 0). */
+int dmmt_encode_device_surfaces(dmmt_ctx* ctx, const dmmt_device_surfaces* surfaces, const dmmt_options* opt,
+                                void* stream);
+/* bytes from a plane's first byte to one past its last:
+ * (height-1)*row_pitch + width*samples_per_pixel*sample_bytes; 0 for an unsupported surface */
+size_t dmmt_surface_span(const dmmt_device_surfaces* surfaces);
+
 /* ---- one image across several GPUs (extension) ---------------------------------------- */
 /* A run of whole MCU rows of one image (BASELINE config 4): with a restart
  * interval (dmmt_options.restart_interval > 0) every stripe that starts and ends on an
