@@ -402,15 +402,18 @@ int enqueue_back_half(dmmt_ctx* c, const Geom& g, int nf, const Work& w, int bit
 
 int enqueue_direct(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, int nf, const Geom& g,
                    const Work& w, int bits, uint8_t* out, size_t out_stride, uint32_t* out_len, hipStream_t st,
-                   const Surface* sf = nullptr) {
+                   const Surface* sf = nullptr, const YccFrames* yf = nullptr) {
     {
         StageTimer t(c, ST_FRONT, st);
         const int cap = c->nlanes > 1 ? DMMT_FRONT_PER_CU_LANES : 0;
-        if (sf)  // a surface: d_rgb is its first plane
+        if (yf)  // YCbCr planes (uint8): d_rgb is the luma plane
+            HIP_TRY(launch_front_ycc(*yf, frame_stride, nf, g, w, st, cap));
+        else if (sf)  // a surface: d_rgb is its first plane
             HIP_TRY(launch_front_surface(*sf, frame_stride, sb, nf, g, w, st, cap));
         else
             HIP_TRY(launch_front(d_rgb, frame_stride, sb, nf, g, w, st, cap));
     }
+    // (check_cat: uint8 YCbCr samples bound the coefficients as integer RGB samples do)
     return enqueue_back_half(c, g, nf, w, bits, out, out_stride, out_len, st, sb == 4);
 }
 
@@ -424,7 +427,8 @@ void destroy_graphs(dmmt_ctx* c) {
 // Stage profiling needs per-kernel events, so it always launches directly.
 int enqueue_encode(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, int nf, const Geom& g,
                    const dmmt_options* opt, uint8_t* out, size_t out_stride, uint32_t* out_len, hipStream_t st,
-                   int lane = 0, bool async = false, int* status = nullptr, const Surface* sf = nullptr) {
+                   int lane = 0, bool async = false, int* status = nullptr, const Surface* sf = nullptr,
+                   const YccFrames* yf = nullptr) {
     Work w;
     int rc;
     if ((rc = prepare(c, g, nf, opt, sb, st, &w, lane, async, status))) return rc;
@@ -432,7 +436,7 @@ int enqueue_encode(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, 
     // (a per-file status area -- dmmt_convert_ppm_device_batch -- would put a new
     // pointer into every file's graph key: that path launches directly)
     if (!c->use_graphs || c->profile || status)
-        return enqueue_direct(c, d_rgb, frame_stride, sb, nf, g, w, bits, out, out_stride, out_len, st, sf);
+        return enqueue_direct(c, d_rgb, frame_stride, sb, nf, g, w, bits, out, out_stride, out_len, st, sf, yf);
     std::vector<uint64_t> key = {(uint64_t)(uintptr_t)d_rgb, (uint64_t)frame_stride, (uint64_t)sb, (uint64_t)nf,
                                  (uint64_t)g.width, (uint64_t)g.height, (uint64_t)g.hr, (uint64_t)g.vr,
                                  (uint64_t)g.maxval, (uint64_t)g.restart_interval, (uint64_t)bits,
@@ -442,6 +446,9 @@ int enqueue_encode(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, 
                                  sf ? (uint64_t)sf->format + 1 : 0, sf ? (uint64_t)sf->row_pitch : 0,
                                  sf ? (uint64_t)(uintptr_t)sf->plane[0] : 0, sf ? (uint64_t)(uintptr_t)sf->plane[1] : 0,
                                  sf ? (uint64_t)(uintptr_t)sf->plane[2] : 0};
+    if (yf)  // YCbCr planes: two descriptions may share their luma pointer
+        key.insert(key.end(), {(uint64_t)yf->format + 16, (uint64_t)yf->luma_pitch, (uint64_t)yf->chroma_pitch,
+                               (uint64_t)(uintptr_t)yf->plane[1], (uint64_t)(uintptr_t)yf->plane[2]});
     const void* const* wp = reinterpret_cast<const void* const*>(&w);
     static_assert(sizeof(Work) % sizeof(void*) == 0, "Work holds pointers only");
     for (size_t i = 0; i < sizeof(Work) / sizeof(void*); ++i) key.push_back((uint64_t)(uintptr_t)wp[i]);
@@ -451,7 +458,7 @@ int enqueue_encode(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, 
     if (!hit) {
         hipGraph_t graph = nullptr;
         HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        rc = enqueue_direct(c, d_rgb, frame_stride, sb, nf, g, w, bits, out, out_stride, out_len, st, sf);
+        rc = enqueue_direct(c, d_rgb, frame_stride, sb, nf, g, w, bits, out, out_stride, out_len, st, sf, yf);
         hipError_t e = hipStreamEndCapture(st, &graph);
         if (rc) {
             if (graph) (void)hipGraphDestroy(graph);
@@ -710,10 +717,11 @@ extern "C" size_t dmmt_max_jpeg_bytes(uint16_t width, uint16_t height, int32_t s
     return max_jpeg_bytes(g);
 }
 
-// dmmt_encode_device and dmmt_encode_device_surfaces (sf: the surface, whose
-// first plane is f->d_rgb) after their own argument checks
+// dmmt_encode_device, dmmt_encode_device_surfaces (sf: the surface, whose first
+// plane is f->d_rgb) and dmmt_encode_device_ycc (yf: the planes, f->d_rgb the luma
+// plane) after their own argument checks
 static int encode_device_frames(dmmt_ctx* c, const dmmt_device_frames* f, const dmmt_options* opt, void* stream,
-                                const Geom& g, const Surface* sf) {
+                                const Geom& g, const Surface* sf, const YccFrames* yf = nullptr) {
     int rc;
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = set_device(c))) return rc;
@@ -724,7 +732,7 @@ static int encode_device_frames(dmmt_ctx* c, const dmmt_device_frames* f, const 
         HIP_TRY(hipEventRecord(c->ev_lane0, c->stream));
         HIP_TRY(hipStreamWaitEvent(st, c->ev_lane0, 0));
         rc = enqueue_encode(c, f->d_rgb, f->frame_stride, f->sample_bytes, f->n_frames, g, opt, f->d_out,
-                            f->out_stride, f->d_out_len, st, 0, true, nullptr, sf);
+                            f->out_stride, f->d_out_len, st, 0, true, nullptr, sf, yf);
         HIP_TRY(hipEventRecord(c->ev_caller, st));
         HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_caller, 0));
         return rc;
@@ -732,7 +740,7 @@ static int encode_device_frames(dmmt_ctx* c, const dmmt_device_frames* f, const 
     int lane = 0;  // pipelined: the next lane's workspace and stream
     if (c->nlanes > 1) lane = (int)(c->next_lane++ % (unsigned)c->nlanes);
     return enqueue_encode(c, f->d_rgb, f->frame_stride, f->sample_bytes, f->n_frames, g, opt, f->d_out, f->out_stride,
-                          f->d_out_len, c->lanes[lane]->stream, lane, true, nullptr, sf);
+                          f->d_out_len, c->lanes[lane]->stream, lane, true, nullptr, sf, yf);
 }
 
 extern "C" int dmmt_encode_device(dmmt_ctx* c, const dmmt_device_frames* f, const dmmt_options* opt, void* stream) {
@@ -785,6 +793,51 @@ extern "C" int dmmt_encode_device_surfaces(dmmt_ctx* c, const dmmt_device_surfac
     f.width = s->width, f.height = s->height, f.maxval = s->maxval, f.sample_bytes = s->sample_bytes;
     f.d_out = s->d_out, f.out_stride = s->out_stride, f.d_out_len = s->d_out_len;
     return encode_device_frames(c, &f, opt, stream, g, &sf);
+}
+
+// the rates of a dmmt_subsampling, 0: out of range
+static int ycc_rates(int sub, int* hr, int* vr) {
+    if (sub < DMMT_P444 || sub > DMMT_P420) return 0;
+    *hr = sub == DMMT_P444 ? 1 : 2;
+    *vr = sub == DMMT_P420 ? 2 : 1;
+    return 1;
+}
+
+extern "C" size_t dmmt_ycc_plane_span(const dmmt_device_ycc* y, int plane) {
+    int hr, vr;
+    if (!y || !y->width || !y->height || !ycc_rates(y->chroma_sampling, &hr, &vr)) return 0;
+    return ycc_plane_span(y->format, plane, y->width, y->height, hr, vr, y->luma_pitch, y->chroma_pitch);
+}
+
+extern "C" int dmmt_encode_device_ycc(dmmt_ctx* c, const dmmt_device_ycc* y, const dmmt_options* opt, void* stream) {
+    c = primary(c);
+    if (!c || !y) return DMMT_E_INVALID_ARGUMENT;
+    int rc;
+    if ((rc = validate(opt))) return rc;
+    if (y->n_frames <= 0 || !y->d_out || !y->d_out_len) return DMMT_E_INVALID_ARGUMENT;
+    if (y->format < DMMT_YCC_PLANAR || y->format > DMMT_YCC_NV_VU) return DMMT_E_INVALID_ARGUMENT;
+    if (y->chroma_sampling != opt->subsampling) return DMMT_E_INVALID_ARGUMENT;  // no conversion between samplings
+    const int nplanes = y->format == DMMT_YCC_PLANAR ? 3 : 2;
+    for (int p = 0; p < nplanes; ++p)
+        if (!y->d_plane[p]) return DMMT_E_INVALID_ARGUMENT;
+    Geom g;
+    if ((rc = make_checked_geom(y->width, y->height, opt->subsampling, 255, opt->restart_interval, &g))) return rc;
+    const size_t chroma_row = (size_t)((g.width + g.hr - 1) / g.hr) * (y->format == DMMT_YCC_PLANAR ? 1 : 2);
+    if (y->luma_pitch < (size_t)g.width || y->luma_pitch > DMMT_MAX_ROW_PITCH || y->chroma_pitch < chroma_row ||
+        y->chroma_pitch > DMMT_MAX_ROW_PITCH)
+        return DMMT_E_INVALID_ARGUMENT;
+    if (y->out_stride < max_jpeg_bytes(g)) return DMMT_E_CAPACITY;
+    YccFrames yf{};
+    for (int p = 0; p < nplanes; ++p) yf.plane[p] = y->d_plane[p];
+    yf.luma_pitch = y->luma_pitch, yf.chroma_pitch = y->chroma_pitch;
+    yf.format = y->format;
+    dmmt_device_frames f{};
+    f.d_rgb = y->d_plane[0];
+    f.frame_stride = y->frame_stride;
+    f.n_frames = y->n_frames;
+    f.width = y->width, f.height = y->height, f.maxval = 255, f.sample_bytes = 1;
+    f.d_out = y->d_out, f.out_stride = y->out_stride, f.d_out_len = y->d_out_len;
+    return encode_device_frames(c, &f, opt, stream, g, nullptr, &yf);
 }
 
 // Host-memory batch of equal-geometry images -> host JPEGs.

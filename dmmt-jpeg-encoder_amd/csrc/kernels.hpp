@@ -53,6 +53,22 @@ int surface_samples_per_pixel(int format, int sample_bytes);
 hipError_t launch_front_surface(const Surface& sf, size_t frame_stride_bytes, int sample_bytes, int n_frames,
                                 const Geom& g, const Work& w, hipStream_t st, int per_cu_cap = 0);
 
+// YCbCr frames (dmmt_device_ycc): format as dmmt_ycc_format
+enum { YCC_PLANAR = 0, YCC_NV = 1, YCC_NV_VU = 2 };
+struct YccFrames {
+    const void* plane[3];  // Y; Cb or the plane of pairs; Cr (planar only)
+    size_t luma_pitch, chroma_pitch;
+    int format;
+};
+// bytes from the first byte of `plane` to one past its last, per frame; 0: a bad
+// format or a plane the format does not use
+size_t ycc_plane_span(int format, int plane, int width, int height, int hr, int vr, size_t luma_pitch,
+                      size_t chroma_pitch);
+// k_front_ycc (front_ycc.hip): uint8 full-range planes -> w.coef, as launch_front;
+// the chroma sampling of the planes is g's
+hipError_t launch_front_ycc(const YccFrames& yf, size_t frame_stride_bytes, int n_frames, const Geom& g, const Work& w,
+                            hipStream_t st, int per_cu_cap = 0);
+
 // per_cu_cap: at most this many resident k_front workgroups per CU (0: as many as
 // fit, 4); a context of several lanes passes DMMT_FRONT_PER_CU_LANES
 hipError_t launch_front(const void* rgb, size_t frame_stride_bytes, int sample_bytes, int n_frames, const Geom& g,

@@ -88,6 +88,9 @@ def lib():
     L.dmmt_encode_device_surfaces.argtypes = [vp, P(DmmtDeviceSurfaces), P(DmmtOptions), vp]
     L.dmmt_surface_span.argtypes = [P(DmmtDeviceSurfaces)]
     L.dmmt_surface_span.restype = sz
+    L.dmmt_encode_device_ycc.argtypes = [vp, P(DmmtDeviceYcc), P(DmmtOptions), vp]
+    L.dmmt_ycc_plane_span.argtypes = [P(DmmtDeviceYcc), ctypes.c_int]
+    L.dmmt_ycc_plane_span.restype = sz
     L.dmmt_ctx_set_lanes.argtypes = [vp, ctypes.c_int]
     L.dmmt_max_jpeg_bytes.argtypes = [u16, u16, i32]
     L.dmmt_max_jpeg_bytes.restype = sz
@@ -195,6 +198,25 @@ class PixelFormat(enum.IntEnum):
 def surface_span(s: DmmtDeviceSurfaces) -> int:
     """dmmt_surface_span: the bytes of a plane the encoder may read, per frame"""
     return int(lib().dmmt_surface_span(ctypes.byref(s)))
+
+
+class DmmtDeviceYcc(ctypes.Structure):
+    _fields_ = [("d_plane", ctypes.c_void_p * 3), ("luma_pitch", ctypes.c_size_t), ("chroma_pitch", ctypes.c_size_t),
+                ("frame_stride", ctypes.c_size_t), ("n_frames", ctypes.c_int32), ("format", ctypes.c_int32),
+                ("chroma_sampling", ctypes.c_int32), ("width", ctypes.c_uint16), ("height", ctypes.c_uint16),
+                ("d_out", ctypes.c_void_p), ("out_stride", ctypes.c_size_t), ("d_out_len", ctypes.c_void_p)]
+
+
+class YccFormat(enum.IntEnum):
+    """dmmt_ycc_format: how the planes of a YCbCr device frame lie"""
+    PLANAR = 0   # Y, Cb, Cr planes (I444 / I422 / I420)
+    NV = 1       # Y plane + a plane of Cb,Cr pairs (NV24 / NV16 / NV12)
+    NV_VU = 2    # Y plane + a plane of Cr,Cb pairs (NV42 / NV61 / NV21)
+
+
+def ycc_plane_span(y: DmmtDeviceYcc, plane: int) -> int:
+    """dmmt_ycc_plane_span: the bytes of a plane the encoder may read, per frame"""
+    return int(lib().dmmt_ycc_plane_span(ctypes.byref(y), int(plane)))
 
 
 class DmmtStripe(ctypes.Structure):
@@ -550,6 +572,84 @@ class Encoder:
         s.width, s.height, s.maxval, s.sample_bytes = width, height, maxval, sample_bytes
         s.d_out, s.out_stride, s.d_out_len = d_out, out_stride, d_out_len
         return s
+
+    @staticmethod
+    def ycc(d_planes, fmt: int, luma_pitch: int, chroma_pitch: int, n_frames: int, width: int, height: int,
+            chroma_sampling: int, d_out: int = 0, out_stride: int = 0, d_out_len: int = 0,
+            frame_stride: int = 0) -> DmmtDeviceYcc:
+        """fill a dmmt_device_ycc struct (nothing is enqueued): d_planes are the device
+        pointers of Y, Cb, Cr (YccFormat.PLANAR) or of Y and the plane of pairs"""
+        y = DmmtDeviceYcc()
+        p = y.d_plane
+        p[0], p[1] = d_planes[0], d_planes[1]
+        if len(d_planes) > 2:
+            p[2] = d_planes[2]
+        y.luma_pitch, y.chroma_pitch, y.frame_stride = luma_pitch, chroma_pitch, frame_stride
+        y.n_frames, y.format, y.chroma_sampling = n_frames, int(fmt), int(chroma_sampling)
+        y.width, y.height = width, height
+        y.d_out, y.out_stride, y.d_out_len = d_out, out_stride, d_out_len
+        return y
+
+    def encode_device_ycc(self, d_planes, fmt: int, luma_pitch: int, chroma_pitch: int, n_frames: int, width: int,
+                          height: int, options: JpegTransformationOptions, d_out: int, out_stride: int,
+                          d_out_len: int, frame_stride: int = 0, stream: int | None = None,
+                          opt_c: DmmtOptions | None = None):
+        """dmmt_encode_device_ycc: uint8 full-range YCbCr planes in HBM, subsampled as
+        options.chroma_subsampling_preset says; enqueued, see synchronize()"""
+        opt = opt_c if opt_c is not None else options.to_c()
+        y = self.ycc(d_planes, fmt, luma_pitch, chroma_pitch, n_frames, width, height, opt.subsampling, d_out,
+                     out_stride, d_out_len, frame_stride)
+        _check(lib().dmmt_encode_device_ycc(self._ctx, ctypes.byref(y), ctypes.byref(opt), stream),
+               "encode_device_ycc")
+
+    def encode_ycc(self, y, cb=None, cr=None, uv=None, vu=None, options: JpegTransformationOptions = None) -> bytes:
+        """One frame from host planes (numpy uint8, JFIF full range): y (H, W) with cb
+        and cr (ch, cw) each, or uv / vu (ch, cw, 2) -- Cb,Cr / Cr,Cb pairs; ch =
+        ceil(H / vr), cw = ceil(W / hr) for options.chroma_subsampling_preset.  The
+        planes are uploaded, encoded where they lie (no RGB round trip) and freed."""
+        if options is None:
+            options = JpegTransformationOptions()
+        given = [k for k, v in (("cb", cb), ("cr", cr), ("uv", uv), ("vu", vu)) if v is not None]
+        if given == ["cb", "cr"]:
+            fmt, chroma = YccFormat.PLANAR, [cb, cr]
+        elif given == ["uv"]:
+            fmt, chroma = YccFormat.NV, [uv]
+        elif given == ["vu"]:
+            fmt, chroma = YccFormat.NV_VU, [vu]
+        else:
+            raise ValueError("give cb and cr, or uv, or vu")
+        sub = ChromaSubsamplingPreset(options.chroma_subsampling_preset)
+        planes = [np.asarray(p) for p in [y] + chroma]
+        if any(p.dtype != np.uint8 for p in planes):
+            raise ValueError("uint8 planes are required")
+        if planes[0].ndim != 2 or 0 in planes[0].shape:
+            raise ValueError("y: shape (H, W)")
+        h, w = planes[0].shape
+        if w > 65535 or h > 65535:
+            raise ValueError("at most 65535 x 65535 pixels")
+        cw, ch = -(-w // sub.horizontal_rate()), -(-h // sub.vertical_rate())
+        want = (ch, cw) if fmt == YccFormat.PLANAR else (ch, cw, 2)
+        for p in planes[1:]:
+            if p.shape != want:
+                raise ValueError(f"chroma shape {p.shape}: {want} is required for {w} x {h} {sub.name}")
+        cap = max_jpeg_bytes(w, h, int(sub))
+        ptrs = []
+        try:
+            for p in planes:
+                ptrs.append(self.malloc(p.size))
+                self.h2d(ptrs[-1], p)
+            d_out = self.malloc(cap)
+            ptrs.append(d_out)
+            d_len = self.malloc(4)
+            ptrs.append(d_len)
+            self.encode_device_ycc(ptrs[:len(planes)], fmt, w, planes[1].size // ch, 1, w, h, options, d_out, cap,
+                                   d_len)
+            self.synchronize()
+            n = int(np.frombuffer(self.d2h(d_len, 4), np.uint32)[0])
+            return self.d2h(d_out, min(n, cap))
+        finally:
+            for ptr in ptrs:
+                self.free(ptr)
 
     def _tensor_surface(self, t, layout, maxval):
         """(planes, format, row_pitch, frame_stride, n_frames, width, height, maxval,

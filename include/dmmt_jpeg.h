@@ -192,6 +192,52 @@ int dmmt_encode_device_surfaces(dmmt_ctx* ctx, const dmmt_device_surfaces* surfa
  * (height-1)*row_pitch + width*samples_per_pixel*sample_bytes; 0 for an unsupported surface */
 size_t dmmt_surface_span(const dmmt_device_surfaces* surfaces);
 
+/* ---- YCbCr device frames (extension) --------------------------------------------------------
+ * Frames that already are YCbCr, as a video decoder or a camera pipeline leaves them: planar
+ * (I444 / I422 / I420) or a luma plane and one plane of chroma pairs (NV24 / NV16 / NV12 and
+ * their Cr,Cb twins).  The reference has no such input (Image<f32> is always RGB), so the
+ * contract is stated in its stages, with hr, vr the rates of opt->subsampling:
+ *  - samples are uint8, JFIF full range (Y, Cb, Cr in 0..255, chroma centred on 128).  NO range
+ *    conversion is done: limited ("video") range input is encoded as if it were full range;
+ *  - the luma plane is width x height, each chroma component ceil(width/hr) x ceil(height/vr).
+ *    The chroma is taken as given: no resampling, no averaging.  chroma_sampling says how the
+ *    planes lie and must equal opt->subsampling: conversion between samplings is out of
+ *    scope (DMMT_E_INVALID_ARGUMENT);
+ *  - a sample s enters the DCT as (float)s - 128, the value range color.rs:75-100 produces;
+ *  - padding as padder.rs:12-42, black: luma is padded to multiples of 8*hr / 8*vr with
+ *    sample 0, chroma to (padded width)/hr x (padded height)/vr with sample 128;
+ *  - from there the reference's path: block resort, the Arai DCT, round(d/q) with the luma
+ *    table for Y and the chroma table for Cb and Cr, MCU emission order, zigzag, the back half
+ *    with its headers; restart intervals as everywhere else.
+ * For plane p and frame f the library reads only bytes of
+ * [d_plane[p] + f * frame_stride, ... + dmmt_ycc_plane_span(y, p)); of those, only the
+ * rectangle's samples influence the output.  A region of interest: point the planes at the
+ * rectangle's first samples and keep the parent's pitches; with subsampled chroma the origin
+ * lies on the chroma grid (even x for hr = 2, even y for vr = 2). */
+enum dmmt_ycc_format {
+    DMMT_YCC_PLANAR = 0,   /* three planes: Y, Cb, Cr      (I444 / I422 / I420) */
+    DMMT_YCC_NV     = 1,   /* Y plane + one plane of Cb,Cr pairs (NV24 / NV16 / NV12) */
+    DMMT_YCC_NV_VU  = 2    /* Y plane + one plane of Cr,Cb pairs (NV42 / NV61 / NV21) */
+};
+typedef struct dmmt_device_ycc {
+    const void* d_plane[3];      /* PLANAR: Y, Cb, Cr; NV*: Y, chroma (d_plane[2] ignored) */
+    size_t luma_pitch, chroma_pitch;  /* bytes between rows; >= the row's bytes, <= DMMT_MAX_ROW_PITCH */
+    size_t frame_stride;         /* bytes between frames, the same for every plane */
+    int32_t n_frames;
+    int32_t format;              /* dmmt_ycc_format */
+    int32_t chroma_sampling;     /* dmmt_subsampling of the planes as they lie; must equal opt->subsampling */
+    uint16_t width, height;      /* the luma rectangle that is encoded */
+    uint8_t* d_out; size_t out_stride; uint32_t* d_out_len;   /* as dmmt_device_frames */
+} dmmt_device_ycc;
+/* Stream, lanes and errors as dmmt_encode_device_surfaces (NULL stream: round-robin over the
+ * lanes; a caller's stream is tied to lane 0 in both directions; errors through
+ * dmmt_ctx_synchronize; a multi-GPU context: member 0). */
+int dmmt_encode_device_ycc(dmmt_ctx* ctx, const dmmt_device_ycc* ycc, const dmmt_options* opt, void* stream);
+/* bytes from the first byte of plane `plane` to one past its last: (rows-1)*pitch + row bytes
+ * (a chroma row: ceil(width/hr) bytes planar, twice that for NV*); 0 for an unsupported
+ * description or a plane the format does not use */
+size_t dmmt_ycc_plane_span(const dmmt_device_ycc* ycc, int plane);
+
 /* ---- one image across several GPUs (extension) ---------------------------------------- */
 /* A run of whole MCU rows of one image (BASELINE config 4): with a restart
  * interval (dmmt_options.restart_interval > 0) every stripe that starts and ends on an
