@@ -173,20 +173,40 @@ __device__ __forceinline__ void walk_block(const BlockCoef& b, int dcd, const ui
         sink(e.x | extra_bits(dcd, cat), (int)e.y);
     }
     const uint2 z = actab[0xF0];
+    // The scalar unit's share of a position is kept to the exec-mask region of the
+    // non-zero test (profiles/STUDIES.md section H).  Three constants live in
+    // scalar registers for the whole unrolled walk: the empty asm hides their
+    // values, so they are not built again with an s_mov at every position.
+    uint32_t m_run = 0xF0u, m_low = 0xFFFFu, m_zrl = 255u;
+    asm volatile("" : "+s"(m_run), "+s"(m_low), "+s"(m_zrl));
     // l16 = 16 * (position of the last non-zero + 1): the zero run before position
     // k is r16 / 16 with r16 = 16 * k - l16, (run & 15) << 4 = r16 & 0xF0
     int l16 = 16;
 #pragma unroll
-    for (int k = 1; k < 64; ++k) {
-        if (k > kmax) continue;  // (wave-uniform) every later position is zero in every lane
-        const int v = coef_at(b, k);
-        if (v != 0) {
-            const int r16 = 16 * k - l16;
-            for (int r = r16 >> 8; r > 0; --r) sink(z.x, (int)z.y);
-            const int cat = category_fast(v);
-            const uint2 e = actab[(r16 & 0xF0) | cat];
-            sink(e.x | extra_bits(v, cat), (int)e.y);
-            l16 = 16 * k + 16;
+    for (int k0 = 0; k0 < 64; k0 += 4) {
+        // (wave-uniform) every position after kmax is zero in every lane: tested once
+        // per four positions -- the ones of the group past kmax fail the non-zero test
+        if (k0 != 0 && k0 > kmax) break;
+#pragma unroll
+        for (int k = k0 ? k0 : 1; k < k0 + 4; ++k) {
+            const uint32_t w = b.w[k >> 1];
+            if ((k & 1) ? w > m_low : (w << 16) != 0u) {
+                const int v = coef_at(b, k);
+                const int r16 = 16 * k - l16;
+                // a run of 16 or more (from position 17 on: l16 >= 16), rare: one vote
+                // and a scalar branch for the wave, not a second exec-mask region
+                // (the asm keeps the vote and the loop's own test two branches)
+                if (k >= 17 && __builtin_amdgcn_ballot_w64((uint32_t)r16 > m_zrl) != 0) {
+                    int r = r16 >> 8;
+                    asm volatile("" : "+v"(r));
+#pragma unroll 1
+                    for (; r > 0; --r) sink(z.x, (int)z.y);
+                }
+                const int cat = category_fast(v);
+                const uint2 e = actab[(r16 & (int)m_run) | cat];
+                sink(e.x | extra_bits(v, cat), (int)e.y);
+                l16 = 16 * k + 16;
+            }
         }
     }
     if (l16 < 16 * 64 || kmax < 63) {
@@ -1053,6 +1073,7 @@ __global__ __launch_bounds__(256, 8) void k_stuffwrite(const uint32_t* __restric
         const unsigned long long kb = pos + 16u * (unsigned)tid;          // first of my 16 bytes (chunk-relative)
         const int nvalid = kb < nbytes ? (int)min(16ull, nbytes - kb) : 0;
         uint32_t x[4] = {0u, 0u, 0u, 0u};  // my 16 bytes, MSB first
+        uint32_t ffm[4] = {0u, 0u, 0u, 0u};  // bit 7 of every valid byte of x that is 0xFF
         uint32_t cnt = 0;
         if (nvalid) {
             const unsigned long long p = off + 8 * kb;  // bit position in the chunk stream (off < 8)
@@ -1073,7 +1094,8 @@ __global__ __launch_bounds__(256, 8) void k_stuffwrite(const uint32_t* __restric
                 const uint32_t vmask = nv ? 0x80808080u & (0xFFFFFFFFu << (32 - 8 * nv)) : 0u;
                 const uint32_t t = ~x[i];
                 const uint32_t nonzero = (((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t) & 0x80808080u;
-                cnt += (uint32_t)__popc(~nonzero & vmask);
+                ffm[i] = ~nonzero & vmask;
+                cnt += (uint32_t)__popc(ffm[i]);
             }
         }
         const uint32_t incl = wave_incl_scan_full_u32(cnt);
@@ -1082,16 +1104,38 @@ __global__ __launch_bounds__(256, 8) void k_stuffwrite(const uint32_t* __restric
         uint32_t pre = incl - cnt;
         for (int q = 0; q < wave; ++q) pre += sWave[q];
         const uint32_t ffs = sWave[0] + sWave[1] + sWave[2] + sWave[3];
-        // stage the stuffed pass in LDS, then store it with consecutive lanes on
-        // consecutive bytes (coalesced)
+        // Stage the stuffed pass in LDS, then store it with consecutive lanes on
+        // consecutive bytes (coalesced).  No branch per byte: byte j goes to dst + j +
+        // (the 0xFF bytes before it in the piece), a population count of the piece's
+        // 0xFF mask, and all 16 are written -- [dst, dst + 16 + cnt) is the piece's
+        // own (pre keeps the next one clear of it), and what a partial last piece
+        // writes past its valid bytes lies past the pass and is never stored.  Only
+        // the pieces that hold a 0xFF (about 6 % at 4K q90) then enter one region
+        // for their 0x00 bytes, a loop over the set bits (STUDIES section H).
         if (nvalid) {
-            uint32_t dst = delta + (uint32_t)tid * 16u + pre;
+            const uint32_t dst = delta + (uint32_t)tid * 16u + pre;
+            uint32_t a = dst;  // where byte 4 i goes
 #pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                if (j < nvalid) {
-                    const uint32_t b = (x[j >> 2] >> (24 - 8 * (j & 3))) & 0xFFu;
-                    sOut[dst++] = (uint8_t)b;
-                    if (b == 0xFFu) sOut[dst++] = 0x00;
+            for (int i = 0; i < 4; ++i) {
+                const uint32_t w = x[i], f = ffm[i];
+                sOut[a + 4 * i] = (uint8_t)(w >> 24);
+                sOut[a + (uint32_t)__popc(f & 0x80000000u) + 4 * i + 1] = (uint8_t)(w >> 16);
+                sOut[a + (uint32_t)__popc(f & 0x80800000u) + 4 * i + 2] = (uint8_t)(w >> 8);
+                sOut[a + (uint32_t)__popc(f & 0x80808000u) + 4 * i + 3] = (uint8_t)w;
+                a += (uint32_t)__popc(f);
+            }
+            if (cnt) {
+                // bit j of m: byte j is 0xFF (the four flags of a word, at bits 24, 16, 8
+                // and 0 once shifted, gathered by one multiplication without carries)
+                uint32_t m = 0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    m |= ((((ffm[i] >> 7) * 0x08040201u) >> 24) & 0xFu) << (4 * i);
+                uint32_t z = dst + 1;  // the 0x00 of the first 0xFF byte, were it byte 0
+                while (m) {
+                    sOut[z + (uint32_t)__builtin_ctz(m)] = 0x00;
+                    ++z;
+                    m &= m - 1u;
                 }
             }
         }
@@ -1100,12 +1144,18 @@ __global__ __launch_bounds__(256, 8) void k_stuffwrite(const uint32_t* __restric
         const uint32_t len = (uint32_t)in_pass + ffs;
         const uint32_t send = delta + len;  // staged bytes [delta, send)
         uint8_t* const oa = o - delta;      // 16-byte aligned
-        for (uint32_t sb = 16u * (uint32_t)tid; sb < send; sb += 16u * 256u) {
-            if (sb >= delta && sb + 16u <= send) {
-                *reinterpret_cast<uint4*>(oa + sb) = *reinterpret_cast<const uint4*>(sOut + sb);
-            } else {  // the pass's first and last 16-byte pieces: only its own bytes
-                for (uint32_t i = max(sb, delta); i < min(sb + 16u, send); ++i) oa[i] = sOut[i];
-            }
+        for (uint32_t sb = 16u * (uint32_t)tid; sb + 16u <= send; sb += 16u * 256u) {
+            if (sb >= delta) *reinterpret_cast<uint4*>(oa + sb) = *reinterpret_cast<const uint4*>(sOut + sb);
+        }
+        // The pass's first and last 16-byte pieces where they are not whole: only the
+        // pass's own bytes, one per lane (no byte loop in the two waves that own them).
+        // Lanes 0..15 take the first piece, [delta, 16) cut at send; lanes 16..31 the
+        // last one from its 16-byte boundary sbt to send, unless it is the first.
+        if (tid < 32) {
+            const uint32_t sbt = send & ~15u;
+            const uint32_t i = tid < 16 ? (uint32_t)tid : sbt + (uint32_t)tid - 16u;
+            const bool mine = tid < 16 ? i >= delta && (delta > 0u || send < 16u) : sbt > 0u;
+            if (mine && i < send) oa[i] = sOut[i];
         }
         o += len;
         __syncthreads();  // sWave / sOut reuse

@@ -21,7 +21,9 @@
 //
 // Floating point: this file is compiled with -ffp-contract=off and without
 // fast-math, f32 '/' is the correctly rounded IEEE division (hipcc default),
-// roundf rounds half away from zero -- the reference's Rust f32 semantics.
+// roundf rounds half away from zero -- the reference's Rust f32 semantics.  The
+// one place that fuses on purpose is rgb_to_ycbcr<true> (integer samples): two
+// fma per pixel whose product, a normalised sample times 0.5, is exact.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -53,12 +55,23 @@ __constant__ uint8_t c_inv_zigzag[64] = {0,  1,  5,  6,  14, 15, 27, 28, 2,  4, 
                                          10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60,
                                          21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
 
-// color.rs:75-100
+// color.rs:75-100.  HALF_FMA (integer samples): the two products by 0.5 are exact
+// -- a normalised sample is 0 or at least 1/65535, far from the subnormals -- so
+// fma(b, 0.5, t) rounds once, exactly as t + b * 0.5 does, and each saves a
+// v_mul: the only two v_fma per pixel this file means to have.  An Image<f32>
+// dot may be small enough for its half to be subnormal and inexact: that path
+// keeps the separate multiply.
+template <bool HALF_FMA>
 __device__ __forceinline__ void rgb_to_ycbcr(float r, float g, float b, float& y, float& cb, float& cr) {
     const float k128 = 128.0f / 255.0f;
     y = (((r * 0.299f + g * 0.587f) + b * 0.114f) - k128) * 255.0f;
-    cb = ((r * -0.1687f + g * -0.3312f) + b * 0.5f) * 255.0f;
-    cr = ((r * 0.5f + g * -0.4186f) + b * -0.0813f) * 255.0f;
+    if constexpr (HALF_FMA) {
+        cb = __builtin_fmaf(b, 0.5f, r * -0.1687f + g * -0.3312f) * 255.0f;
+        cr = (__builtin_fmaf(r, 0.5f, g * -0.4186f) + b * -0.0813f) * 255.0f;
+    } else {
+        cb = ((r * -0.1687f + g * -0.3312f) + b * 0.5f) * 255.0f;
+        cr = ((r * 0.5f + g * -0.4186f) + b * -0.0813f) * 255.0f;
+    }
 }
 
 // ============================================================== k_front
@@ -447,7 +460,7 @@ __device__ __forceinline__ void front_body(const Sample* __restrict__ rgb, size_
                             }
                         }
                         float y, cb, cr;
-                        rgb_to_ycbcr(rr, gg, bb, y, cb, cr);
+                        rgb_to_ycbcr<SB != 4>(rr, gg, bb, y, cb, cr);
                         yv[dy][jx] = y;
                         if (dx == 0 && dy == 0) {
                             cbs = cb;
