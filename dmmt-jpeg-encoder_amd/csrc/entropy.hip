@@ -48,9 +48,13 @@ static_assert(kChunkBlocks == 256 || kChunkBlocks == 512, "one thread per block,
 constexpr int kEmitThreads = kChunkBlocks;
 constexpr int kEmitWaves = kEmitThreads / 64;
 #ifndef DMMT_EMIT_OCC
-#define DMMT_EMIT_OCC 7  // k_emit workgroups per CU the launch bounds target (256-block chunks; study builds: others)
+#define DMMT_EMIT_OCC 8  // k_emit workgroups per CU the launch bounds target: 64 VGPRs, under 20 KB of LDS (256-block chunks; study builds: others)
 #endif
 constexpr int kEmitOcc = kChunkBlocks == 256 ? DMMT_EMIT_OCC : 3;  // workgroups per CU
+#ifndef DMMT_EMIT_OCC_BATCH
+#define DMMT_EMIT_OCC_BATCH 7  // the same for a batched launch from a context of several lanes (launch_emit)
+#endif
+constexpr int kEmitOccBatch = kChunkBlocks == 256 ? DMMT_EMIT_OCC_BATCH : 3;
 
 // LDS word window of k_emit: 32 Ki bits = 128 bits per block on average (the 4K
 // q90 workload averages ~110).  A chunk with more is assembled in several
@@ -67,6 +71,9 @@ constexpr int kStuffPass = 4096;
 #endif
 #ifndef DMMT_TAIL_NSEG1
 #define DMMT_TAIL_NSEG1 1  // fused offsets: no chunk_span division per chunk without restart intervals (0: study builds)
+#endif
+#ifndef DMMT_WALK_COLUMN_MAJOR
+#define DMMT_WALK_COLUMN_MAJOR 1  // the walk reads the column-major block's registers in place (0: permuted to zigzag order first)
 #endif
 #ifndef DMMT_EMIT_PRIO_ALWAYS
 #define DMMT_EMIT_PRIO_ALWAYS 0  // study builds: the priorities with several lanes too (the round-5 behaviour)
@@ -132,12 +139,15 @@ __device__ __forceinline__ void load_block(const int16_t* __restrict__ p, BlockC
     }
 }
 
-// the coefficient at zigzag position k, after zigzag_in_registers
+// the coefficient in half-word k of the block's registers
 __device__ __forceinline__ int coef_at(const BlockCoef& b, int k) {
     return (k & 1) ? ((int)b.w[k >> 1] >> 16) : (int)(int16_t)(b.w[k >> 1] & 0xFFFFu);
 }
 
-// Blocks arrive column-major (coef_pos); the walk wants zigzag order: one
+// Blocks arrive column-major (coef_pos).  The walk reads those registers in place,
+// position k at half-word coef_pos(k) (DMMT_WALK_COLUMN_MAJOR: the permutation
+// below held up to 64 registers at its middle, the kernel's peak; profiles/
+// STUDIES.md section I).  With the switch off the walk wants zigzag order: one
 // constant permutation of the 64 halves in registers, 32 word builds.  (Walking
 // the column-major registers directly, coef_at(b, coef_pos(k)), is the same
 // computation.  One round-2 build of that form computed wrong bits, differently
@@ -147,6 +157,9 @@ __device__ __forceinline__ int coef_at(const BlockCoef& b, int k) {
 // library, refuses that pattern).  The study switch is
 // profiles/r05_study_variants.patch; tests/test_gpu_regressions.py guards the shape.)
 __device__ __forceinline__ void zigzag_in_registers(BlockCoef& b) {
+#if DMMT_WALK_COLUMN_MAJOR
+    return;
+#endif
     uint32_t z[32];
 #pragma unroll
     for (int j = 0; j < 32; ++j) {
@@ -172,7 +185,6 @@ __device__ __forceinline__ void walk_block(const BlockCoef& b, int dcd, const ui
         const uint2 e = dctab[cat];
         sink(e.x | extra_bits(dcd, cat), (int)e.y);
     }
-    const uint2 z = actab[0xF0];
     // The scalar unit's share of a position is kept to the exec-mask region of the
     // non-zero test (profiles/STUDIES.md section H).  Three constants live in
     // scalar registers for the whole unrolled walk: the empty asm hides their
@@ -189,9 +201,10 @@ __device__ __forceinline__ void walk_block(const BlockCoef& b, int dcd, const ui
         if (k0 != 0 && k0 > kmax) break;
 #pragma unroll
         for (int k = k0 ? k0 : 1; k < k0 + 4; ++k) {
-            const uint32_t w = b.w[k >> 1];
-            if ((k & 1) ? w > m_low : (w << 16) != 0u) {
-                const int v = coef_at(b, k);
+            const int kc =DMMT_WALK_COLUMN_MAJOR ? coef_pos(k) : k;  // the coefficient's half-word
+            const uint32_t w = b.w[kc >> 1];
+            if ((kc & 1) ? w > m_low : (w << 16) != 0u) {
+                const int v = coef_at(b, kc);
                 const int r16 = 16 * k - l16;
                 // a run of 16 or more (from position 17 on: l16 >= 16), rare: one vote
                 // and a scalar branch for the wave, not a second exec-mask region
@@ -199,6 +212,9 @@ __device__ __forceinline__ void walk_block(const BlockCoef& b, int dcd, const ui
                 if (k >= 17 && __builtin_amdgcn_ballot_w64((uint32_t)r16 > m_zrl) != 0) {
                     int r = r16 >> 8;
                     asm volatile("" : "+v"(r));
+                    // (the ZRL entry is read here, where it is rare, not held in two
+                    // registers through the whole walk)
+                    const uint2 z = actab[0xF0];
 #pragma unroll 1
                     for (; r > 0; --r) sink(z.x, (int)z.y);
                 }
@@ -262,8 +278,8 @@ struct WindowSink {
 // from bit 0 of its own slot (no sharing, plain stores), word i of thread t at
 // sSlot[i * kEmitThreads + t] (consecutive threads, consecutive banks).  A block
 // that needs more than kSlotWords words (384 bits, slot_copy.hpp) sets `over`; the
-// chunk then takes the re-walk path.  Small slots and window keep 7 workgroups
-// resident per CU.
+// chunk then takes the re-walk path.  Small slots and a window that overlays them
+// keep 8 workgroups resident per CU.
 struct SlotSink {
     uint32_t* slot;  // &sSlot[tid]
     unsigned long long acc;
@@ -322,14 +338,24 @@ __device__ __forceinline__ void fused_offsets(const uint32_t* __restrict__ cbits
                               const unsigned long long* __restrict__ cff8, uint8_t* sFF8,
                               const uint32_t* __restrict__ cedge, const Geom& g, unsigned long long* __restrict__ bit0,
                               unsigned long long* __restrict__ outo, unsigned long long* __restrict__ total,
-                              unsigned long long* sWaveV, int* sWaveF, Mark mark = Mark());
+                              unsigned long long* sWaveV, int* sWaveF, int tid, Mark mark = Mark());
 static_assert(kArriveWords == kArriveFrameWords, "the host sizes the counters");
+
+// threadIdx.x from the wave's number in the workgroup (scalar) and the lane's
+// number, counted again: the zero operand goes through an empty asm, so the count
+// is not merged with an earlier one and held in a register in between.
+__device__ __forceinline__ int tid_again(int wave) {
+    uint32_t zero = 0u;
+    asm volatile("" : "+s"(zero));
+    return (wave << 6) | (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, zero));
+}
 
 // ---------------------------------------------------------------------- k_emit
 // fuse: the frame's last workgroup to finish also computes every chunk's offsets
 // (fused_offsets; `arrive` counts the finished workgroups per frame and is zero
 // between launches), so no k_offsets launch follows
-__global__ __launch_bounds__(kEmitThreads, kEmitOcc) void k_emit(const int16_t* coef, const int16_t* __restrict__ dcdiff,
+template <int OCC>
+__global__ __launch_bounds__(kEmitThreads, OCC) void k_emit(const int16_t* coef, const int16_t* __restrict__ dcdiff,
                                               const uint8_t* __restrict__ lastnz,
                                               const uint32_t* __restrict__ code_tab, Geom g,
                                               uint32_t* __restrict__ stage, uint32_t* __restrict__ chunk_bits,
@@ -342,11 +368,15 @@ __global__ __launch_bounds__(kEmitThreads, kEmitOcc) void k_emit(const int16_t* 
                                               unsigned long long* __restrict__ chunk_ff8, int prio) {
     // code tables: [luma AC 256][chroma AC 256][luma DC 16][chroma DC 16]
     __shared__ uint2 sTab[2 * 256 + 2 * 16];
-    // the window image; during the sort and the walk its first words hold the
-    // walk order, the keys and the blocks' bit counts (read before the window
-    // loop, whose first clear follows two barriers)
-    __shared__ uint32_t sW[kEmitWords + 2];
+    // the private slots; the window image overlays their first words: every
+    // thread holds its block's slot words in registers (read_slot, then a
+    // barrier) before the first window word is written, and the re-walk path
+    // never reads a slot
     __shared__ __attribute__((aligned(16))) uint32_t sSlot[kSlotWords * kEmitThreads];
+    static_assert(kEmitWords + 2 <= kSlotWords * kEmitThreads, "the window image lies inside the slot area");
+    uint32_t* const sW = sSlot;
+    // the walk order, the keys and the blocks' bit counts (live during the walk)
+    __shared__ uint32_t sSort[kEmitThreads + kEmitThreads * (int)sizeof(std::conditional_t<(kEmitThreads > 256), uint16_t, uint8_t>) / 4 + kEmitThreads / 4];
     __shared__ uint32_t sWave[kEmitWaves];
     __shared__ uint32_t sFF[8];
     __shared__ uint32_t sEdge[3];  // word 0, the two words holding bits total-16 .. total-1
@@ -355,17 +385,19 @@ __global__ __launch_bounds__(kEmitThreads, kEmitOcc) void k_emit(const int16_t* 
     __shared__ int sOffF[kEmitWaves];
     __shared__ uint32_t sLast;
     using OrderT = std::conditional_t<(kEmitThreads > 256), uint16_t, uint8_t>;
-    uint32_t* const sBits = sW;                                                      // bit count of block t
-    OrderT* const sOrder = reinterpret_cast<OrderT*>(sW + kEmitThreads);               // block walked by thread u
-    uint8_t* const sKey = reinterpret_cast<uint8_t*>(sW + kEmitThreads + kEmitThreads * (int)sizeof(OrderT) / 4);  // its last non-zero position
+    uint32_t* const sBits = sSort;                                                      // bit count of block t
+    OrderT* const sOrder = reinterpret_cast<OrderT*>(sSort + kEmitThreads);               // block walked by thread u
+    uint8_t* const sKey = reinterpret_cast<uint8_t*>(sSort + kEmitThreads + kEmitThreads * (int)sizeof(OrderT) / 4);  // its last non-zero position
     DMMT_TRACE_START;
-    const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
+    // (wave: scalar.  After the walk the thread's index is built again from it and
+    // the lane's number, tid_again, so the walk holds neither in a vector register.)
+    int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int frame = blockIdx.y;
     const unsigned chunk = blockIdx.x;
     const ChunkSpan span = chunk_span(g, (int)chunk);
     const long long el0 = span.el0;
     const int nb = span.nb;
-    const long long e = (long long)frame * g.bpf + el0 + tid;
     const size_t cid = (size_t)frame * g.nch + chunk;
     // the chunk's first block's place in its MCU (bpf < 2^31: 32-bit, once per
     // wave) and a 16-bit reciprocal of the blocks per MCU for the per-lane mod
@@ -375,12 +407,12 @@ __global__ __launch_bounds__(kEmitThreads, kEmitOcc) void k_emit(const int16_t* 
     // not three): the code tables -- code_tab is [luma DC][luma AC][chroma DC]
     // [chroma AC] x 256; two AC words per thread, one DC word for threads below 32
     // -- and the block's last non-zero position (at a clamped index past nb)
-    const bool valid = tid < nb;
+    bool valid = tid < nb;
     const uint32_t* ct = code_tab + (size_t)frame * 1024;
     const int tt = tid & 255;
     const uint32_t tac0 = ct[256 + tt], tac1 = ct[768 + tt];
     const uint32_t tdc = ct[((tt & 31) < 16 ? 0 : 512 - 16) + (tt & 31)];
-    const uint32_t lz = lastnz[valid ? e : (long long)frame * g.bpf + el0];
+    const uint32_t lz = lastnz[(long long)frame * g.bpf + el0 + (valid ? tid : 0)];
     if (tid < 256) {  // (pre-shifted by the symbol's category, walk_block)
         const int c = tid & 15;
         sTab[tid] = make_uint2((tac0 & 0xFFFFu) << c, (tac0 >> 16) + c);
@@ -410,8 +442,8 @@ __global__ __launch_bounds__(kEmitThreads, kEmitOcc) void k_emit(const int16_t* 
         sBin[tid] = inc - c;  // first position of bin tid
     }
     __syncthreads();
-    const int mine = valid ? (int)(sBin[key] + rank) : tid;
     if (valid) {
+        const int mine = (int)(sBin[key] + rank);
         sOrder[mine] = (OrderT)tid;
         sKey[mine] = (uint8_t)key;
     }
@@ -450,7 +482,9 @@ __global__ __launch_bounds__(kEmitThreads, kEmitOcc) void k_emit(const int16_t* 
             walk_block(b, dp, sTab + 512 + (lum ? 0 : 16), sTab + (lum ? 0 : 256), ss, kmax);
             wbits = ss.finish();
             slot_over = wbits > (uint32_t)kSlotWords * 32u;
-            sBits[p] = wbits;
+            // (with the walker's column in the high half: the block's thread finds its
+            // slot there instead of holding its rank in a register through the walk)
+            sBits[p] = wbits | ((uint32_t)tid << 16);
             DMMT_TRACE(5);
         }
     }
@@ -459,9 +493,13 @@ __global__ __launch_bounds__(kEmitThreads, kEmitOcc) void k_emit(const int16_t* 
 #endif
     // a block too long for its slot sends the whole chunk down the re-walk path
     const bool over = __syncthreads_or(slot_over) != 0;
-    const uint32_t bits = valid ? sBits[tid] : 0u;
-    const int k = valid ? mod_small(r0 + tid, g.bpm, inv16) : 0;
-    const bool lum_t = k < g.n_luma;
+    tid = tid_again(wave);
+    const int lane = tid & 63;
+    valid = tid < nb;
+    static_assert(kMaxBlockBits < (1 << 16), "a block's bit count and its walker's column share a word");
+    const uint32_t bw = valid ? sBits[tid] : (uint32_t)tid << 16;
+    const uint32_t bits = bw & 0xFFFFu;
+    const int mine = (int)(bw >> 16);
     // offsets inside the chunk by a workgroup scan
     const uint32_t incl = wave_incl_scan_full_u32(bits);
     if (lane == 63) sWave[wave] = incl;
@@ -478,34 +516,10 @@ __global__ __launch_bounds__(kEmitThreads, kEmitOcc) void k_emit(const int16_t* 
     uint32_t* slot = stage + cid * (size_t)kChunkWordsCap;
     const int nw = (int)((total + 31) >> 5);
     const int we1 = total >= 16 ? (int)((total - 16) >> 5) : 0;  // word holding bit total-16
-    uint32_t ff[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int w0 = 0; w0 < nw; w0 += kEmitWords) {  // uniform; one window unless the chunk is huge
-        const int wn = min(kEmitWords, nw - w0);
-        if (!over) {  // (uniform) block tid's bits from its walker's slot (column `mine`)
-            SlotWords sw;
-            read_slot<kEmitThreads>(sSlot, mine, bits, sw);
-            if (tid == 0 && w0 + wn >= nw) sW[wn] = 0u;  // past the stream: no block owns it
-            copy_owned(sw, start, bits, sW, w0, wn);
-            __syncthreads();
-            copy_head(sw, start, bits, sW, w0, wn);
-        } else {
-            for (int i = tid; i <= wn; i += kEmitThreads) sW[i] = 0u;  // + the next window's first word
-            __syncthreads();
-        }
-        if (over && bits && start < (uint32_t)(w0 + wn + 1) * 32u && start + bits > (uint32_t)w0 * 32u) {
-            {
-                // the block again (L2 / MALL) and a second walk straight into the
-                // window: holding it in registers across the scan would halve the
-                // occupancy of this kernel
-                BlockCoef b;
-                load_block(coef + e * 64, b);
-                zigzag_in_registers(b);
-                WindowSink ws{sW, w0, wn + 1, 0ull, (int)(start & 31), (int)(start >> 5), true};
-                walk_block(b, dcdiff[e], sTab + 512 + (lum_t ? 0 : 16), sTab + (lum_t ? 0 : 256), ws);
-                ws.finish();
-            }
-        }
-        __syncthreads();
+    uint32_t ff[4] = {0, 0, 0, 0};  // residues 2r and 2r + 1 in the halves of ff[r]
+    // a finished window: its words to the chunk's staging slot, the edge words, the
+    // 0xFF bytes at every residue
+    auto window_out = [&](int tid, int w0, int wn) {
         for (int i = tid; i < wn; i += kEmitThreads) {
             const uint32_t a = sW[i], c = sW[i + 1];
             slot[w0 + i] = a;
@@ -523,17 +537,70 @@ __global__ __launch_bounds__(kEmitThreads, kEmitOcc) void k_emit(const int16_t* 
             const uint32_t m = (uint32_t)(z >> 32);
             if (m) {
 #pragma unroll
-                for (int r = 0; r < 8; ++r) ff[r] += __popc(m & (0x80808080u >> r));
+                for (int r = 0; r < 4; ++r)
+                    ff[r] += __popc(m & (0x80808080u >> (2 * r))) | (__popc(m & (0x80808080u >> (2 * r + 1))) << 16);
             }
         }
+    };
+    // The window loop, uniform; one window unless the chunk is huge.  One loop for
+    // each path, so that the slot words are not live through the re-walk.  In both
+    // the block's start goes through an empty asm: what it feeds (the shifted words
+    // and the conditions of the copy) is then computed window by window, and not
+    // hoisted out of the loop into two dozen registers that live across it.
+    if (!over) {  // (uniform)
+        // block tid's bits from its walker's slot (column `mine`), taken into
+        // registers once for every window: the first window written overwrites the slots
+        SlotWords sw;
+        read_slot<kEmitThreads>(sSlot, mine, bits, sw);
         __syncthreads();
+        for (int w0 = 0; w0 < nw; w0 += kEmitWords) {
+            const int wn = min(kEmitWords, nw - w0);
+            uint32_t st = start;
+            asm volatile("" : "+v"(st));
+            if (tid == 0 && w0 + wn >= nw) sW[wn] = 0u;  // past the stream: no block owns it
+            copy_owned(sw, st, bits, sW, w0, wn);
+            __syncthreads();
+            copy_head(sw, st, bits, sW, w0, wn);
+            __syncthreads();
+            window_out(tid, w0, wn);
+            __syncthreads();
+        }
+    } else {
+        for (int w0 = 0; w0 < nw; w0 += kEmitWords) {
+            const int wn = min(kEmitWords, nw - w0);
+            uint32_t st = start;
+            asm volatile("" : "+v"(st));
+            for (int i = tid; i <= wn; i += kEmitThreads) sW[i] = 0u;  // + the next window's first word
+            __syncthreads();
+            // (the thread's index is not held through the second walk either)
+            if (bits && st < (uint32_t)(w0 + wn + 1) * 32u && st + bits > (uint32_t)w0 * 32u) {
+                // (the block's index and component likewise: built here, on the rare path)
+                const int te = tid_again(wave);
+                const long long e = (long long)frame * g.bpf + el0 + te;
+                const bool lum_t = mod_small(r0 + te, g.bpm, inv16) < g.n_luma;
+                // the block again (L2 / MALL) and a second walk straight into the
+                // window: holding it in registers across the scan would halve the
+                // occupancy of this kernel
+                BlockCoef b;
+                load_block(coef + e * 64, b);
+                zigzag_in_registers(b);
+                WindowSink ws{sW, w0, wn + 1, 0ull, (int)(st & 31), (int)(st >> 5), true};
+                walk_block(b, dcdiff[e], sTab + 512 + (lum_t ? 0 : 16), sTab + (lum_t ? 0 : 256), ws);
+                ws.finish();
+            }
+            tid = tid_again(wave);
+            __syncthreads();
+            window_out(tid, w0, wn);
+            __syncthreads();
+        }
     }
     DMMT_TRACE(2);
     // the eight residue counts two to a word (16-bit fields: a wave's count stays
-    // below 64 * 4 * 56 < 2^16), summed over the wave by DPP
+    // below 64 * 4 * 62 < 2^16 -- a chunk has at most kChunkWordsCap = 62 * 256
+    // words), summed over the wave by DPP
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        const uint32_t v = wave_sum_full_u32(ff[2 * r] | (ff[2 * r + 1] << 16));
+        const uint32_t v = wave_sum_full_u32(ff[r]);
         if (lane == 0 && v) {
             atomicAdd(&sFF[2 * r], v & 0xFFFFu);
             atomicAdd(&sFF[2 * r + 1], v >> 16);
@@ -574,7 +641,7 @@ __global__ __launch_bounds__(kEmitThreads, kEmitOcc) void k_emit(const int16_t* 
 #endif
             // (the packed counts go to sSlot, which no wave reads any more)
             fused_offsets(chunk_bits + fb, chunk_ff + fb * 8, chunk_ff8 + fb, reinterpret_cast<uint8_t*>(sSlot),
-                          chunk_edge + fb, g, chunk_bit0 + fb, chunk_out + fb, total_out + frame, sOffV, sOffF, mark);
+                          chunk_edge + fb, g, chunk_bit0 + fb, chunk_out + fb, total_out + frame, sOffV, sOffF, tid, mark);
         }
     }
     DMMT_TRACE(3);
@@ -625,8 +692,8 @@ __device__ __forceinline__ unsigned long long chunk_out_bytes(const uint32_t* __
 // workgroup (NW waves) exclusive scan; *tot receives the total
 template <int NW>
 __device__ __forceinline__ unsigned long long block_scan_nw(unsigned long long v, unsigned long long* sWave,
-                                                            unsigned long long* tot) {
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
+                                                            unsigned long long* tot, int tid = threadIdx.x) {
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // (scalar: the loops over the earlier waves are uniform)
     const unsigned long long incl = wave_incl_scan_full_u64(v);  // (every thread takes part)
     if (lane == 63) sWave[wave] = incl;
     __syncthreads();
@@ -651,8 +718,8 @@ __device__ __forceinline__ void seg_combine(bool& f, unsigned long long& v, bool
 template <int NW>
 __device__ __forceinline__ unsigned long long block_segscan_nw(bool f, unsigned long long v,
                                                                unsigned long long* sWaveV, int* sWaveF,
-                                                               bool* flag_out = nullptr) {
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
+                                                               bool* flag_out = nullptr, int tid = threadIdx.x) {
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // (scalar: the loops over the earlier waves are uniform)
     bool fi = f;
     unsigned long long vi = v;
     // inclusive within the wave over DPP: row shifts 1, 2, 4, 8 (a lane without a
@@ -701,7 +768,7 @@ __device__ __forceinline__ unsigned long long block_segscan_1024(bool f, unsigne
 // The chunk offsets of one frame computed by k_emit's last workgroup to finish
 // (frames of at most kFusedOffsetsMaxChunks chunks; k_offsets otherwise): what
 // k_offsets computes, with 256 threads, in rounds of kFusedRoundChunks chunks (6
-// per thread in registers; 8 spill at k_emit's 72 VGPRs), each round carrying the
+// per thread in registers; 8 spill at k_emit's register budget), each round carrying the
 // bit position and the byte count of the ones before it.  The other workgroups'
 // summaries (bits, 0xFF counts, edges) were stored write-through (agent scope)
 // before they counted themselves in, so they are read with agent-scope loads; the
@@ -718,10 +785,9 @@ __device__ __forceinline__ void fused_offsets(const uint32_t* __restrict__ cbits
                               const unsigned long long* __restrict__ cff8, uint8_t* sFF8,
                               const uint32_t* __restrict__ cedge, const Geom& g, unsigned long long* __restrict__ bit0,
                               unsigned long long* __restrict__ outo, unsigned long long* __restrict__ total,
-                              unsigned long long* sWaveV, int* sWaveF, Mark mark) {
+                              unsigned long long* sWaveV, int* sWaveF, int tid, Mark mark) {
     // (32-bit offsets: the static_assert above; they keep the chunks' state in few registers)
     constexpr int KP = kFusedRoundChunks / kEmitThreads, NT = kEmitThreads;
-    const int tid = threadIdx.x;
     const int nch = g.nch;
     uint32_t carry_run = 0, carry_out = 0;  // the bit position after, and the bytes of, the rounds before
     for (int r0 = 0; r0 < nch; r0 += kFusedRoundChunks) {  // uniform
@@ -775,7 +841,7 @@ __device__ __forceinline__ void fused_offsets(const uint32_t* __restrict__ cbits
         for (int i = 0; i < KP; ++i)
             if (c0 + i < c1) seg_combine(f, v, (firstm >> i) & 1u, nbits[i] + (c0 + i == 0 ? (uint32_t)g.bit_phase : 0u));
         bool fx;
-        const uint32_t ex = (uint32_t)block_segscan_nw<kEmitWaves>(f, v, sWaveV, sWaveF, &fx);
+        const uint32_t ex = (uint32_t)block_segscan_nw<kEmitWaves>(f, v, sWaveV, sWaveF, &fx, tid);
         mark(std::integral_constant<int, 7>{});  // the bits and edges loaded, the bit scan
         uint32_t run = fx ? ex : carry_run + ex;  // (a segment start before it in this round resets the carry)
         uint32_t b0[KP];
@@ -829,7 +895,7 @@ __device__ __forceinline__ void fused_offsets(const uint32_t* __restrict__ cbits
         }
         mark(std::integral_constant<int, 8>{});  // the 0xFF counts at each chunk's residue loaded, the bytes
         unsigned long long tot = 0;
-        uint32_t orun = carry_out + (uint32_t)block_scan_nw<kEmitWaves>(mine, sWaveV, &tot);  // (its barriers publish the carry)
+        uint32_t orun = carry_out + (uint32_t)block_scan_nw<kEmitWaves>(mine, sWaveV, &tot, tid);  // (its barriers publish the carry)
         mark(std::integral_constant<int, 9>{});  // the byte scan
 #pragma unroll
         for (int i = 0; i < KP; ++i) {
@@ -1167,7 +1233,13 @@ bool offsets_fusable(const Geom& g) { return g.nch <= kFusedOffsetsMaxChunks; }
 
 hipError_t launch_emit(int n_frames, const Geom& g, const Work& w, bool fuse_offsets, hipStream_t st, bool prio) {
     const int fuse = fuse_offsets && offsets_fusable(g) ? 1 : 0;
-    hipLaunchKernelGGL(k_emit, dim3(g.nch, n_frames), dim3(kEmitThreads), 0, st, (const int16_t*)w.coef,
+    // A batched launch (many frames' chunks: every CU full for the whole kernel) from
+    // a context of several lanes runs the build for seven workgroups per CU, not
+    // eight: the eighth takes the last wave slot of every SIMD, and no other lane's
+    // kernel runs beside it (1080p 4:2:0 x256, 4 lanes: -2.6 % with eight, level
+    // with seven, profiles/r08_emit_occ8_ab.txt).
+    const auto kern = !prio && n_frames > 1 ? k_emit<kEmitOccBatch> : k_emit<kEmitOcc>;
+    hipLaunchKernelGGL(kern, dim3(g.nch, n_frames), dim3(kEmitThreads), 0, st, (const int16_t*)w.coef,
                        (const int16_t*)w.dcdiff, (const uint8_t*)w.lastnz, (const uint32_t*)w.code_tab, g, w.stage, w.chunk_bits, w.chunk_ff,
                        w.chunk_edge, w.ac_hist, w.dc_hist, fuse, w.arrive, w.chunk_bit0, w.chunk_out, w.total_out,
                        w.chunk_ff8, prio || DMMT_EMIT_PRIO_ALWAYS ? 1 : 0);

@@ -624,6 +624,9 @@ constexpr int kTailLdsBytes = 7072;  // tables_tail's per-table regions (static_
 // Huffman tables and the header (tables_tail), so no k_tables launch follows.
 // Eight waves per SIMD (at most 64 VGPRs): the tail alone would take more, and the
 // histogram loop wants the occupancy.
+#ifndef DMMT_HIST_NEWEST_FIRST
+#define DMMT_HIST_NEWEST_FIRST 0  // study builds: 1 = every thread takes its passes in descending block order
+#endif
 template <bool CHECK, bool FUSE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_hist(const int16_t* __restrict__ coef, int16_t* __restrict__ dcdiff,
                                               uint8_t* __restrict__ lastnz, Geom g,
@@ -654,9 +657,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     const uint32_t bpf = (uint32_t)g.bpf, bpm = (uint32_t)g.bpm, ri = (uint32_t)max(g.restart_interval, 1);
     const uint32_t stride = gridDim.x * 256u, sm = stride / bpm, sk = stride - sm * bpm;
     uint32_t el = blockIdx.x * 256u + (uint32_t)tid;
+#if DMMT_HIST_NEWEST_FIRST
+    // study build: the passes in descending block order (k_front's most recently
+    // written lines first).  Every thread of the grid counts the same passes down --
+    // a wave's lanes stay on neighbouring blocks for the DC shuffle -- and sits out
+    // the first when it lies past the frame; (m, k, mr) step back from the first
+    // block the thread takes.
+    const uint32_t passes = (bpf + stride - 1u) / stride;
+    el += (passes - 1u) * stride;
+    const uint32_t el1 = el < bpf ? el : el - stride;
+    uint32_t m = el1 / bpm, k = el1 - m * bpm, mr = m % ri;
+#else
     uint32_t m = el / bpm, k = el - m * bpm, mr = m % ri;
+#endif
     const uint32_t smr = sm % ri;
+#if DMMT_HIST_NEWEST_FIRST
+    for (uint32_t left = passes; left > 0; --left, el -= stride) {
+        if (el >= bpf) continue;
+#else
     for (; el < bpf; el += stride) {
+#endif
         const long long e = base + el;
         const uint4* q = reinterpret_cast<const uint4*>(coef + e * 64);
         uint32_t cw[32];  // column-major (coef_pos)
@@ -713,9 +733,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             dcdiff[e] = d;
             atomicAdd(&H[512 + 16 * t + category_of(d)], 1u);
         }
+#if DMMT_HIST_NEWEST_FIRST
+        // (unsigned: a borrow wraps past bpm / ri; m is not read once it would pass 0)
+        m -= sm, k -= sk, mr -= smr;
+        if (k >= bpm) k += bpm, --m, --mr;
+        if (mr >= ri) mr += ri;
+#else
         m += sm, k += sk, mr += smr;
         if (k >= bpm) k -= bpm, ++m, ++mr;
         if (mr >= ri) mr -= ri;
+#endif
     }
     if (bad) raise_status(status, bad);
     __syncthreads();
