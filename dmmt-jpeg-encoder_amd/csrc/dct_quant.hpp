@@ -1,15 +1,45 @@
 // dct_quant.hpp -- the 8-point Arai butterfly and the quantisers of the front
 // kernels (kernels.hip: k_front, k_front_surf, k_dct_blocks; front_ycc.hip:
-// k_front_ycc).  Device code only; every including file is compiled with
-// -ffp-contract=off (see kernels.hip's header comment on floating point).
+// k_front_ycc).  Every including file is compiled with -ffp-contract=off (see
+// kernels.hip's header comment on floating point).  Device code, and compiled for
+// the host by a CPU unit check (tests/native/quant_check.cpp: both quantisers
+// against quantize() around every half-integer), which needs the same flag.
 #pragma once
+#ifdef __HIPCC__
 #include <hip/hip_runtime.h>
+#define DMMT_DQ_FN __device__ __forceinline__
+#define DMMT_DQ_FRACT(a) __builtin_amdgcn_fractf(a)
+#else
+#include <math.h>
+#define DMMT_DQ_FN inline
+// v_fract_f32 for the host.  Only ever applied to a finite a >= 0 (the operand is
+// tested `a < 2^22` first and a NaN fails that test), where a - floor(a) is exact
+// and is what the instruction returns.
+#define DMMT_DQ_FRACT(a) ((a) - floorf(a))
+#endif
 #include <stdint.h>
+
+// The two safety margins of the shortcut quantisers below (the literals their
+// comments derive).  Overridable only so that the CPU unit check can be built once
+// more without them and must then find wrong coefficients.
+#ifndef DMMT_QUANT_F32_BAND
+#define DMMT_QUANT_F32_BAND 0x1p-20f  // quantize_col8: distance from a half-integer, relative to |t|
+#endif
+#ifndef DMMT_QUANT_SCALED_BAND
+#define DMMT_QUANT_SCALED_BAND 0x1p-21f  // quantize_col8_scaled: the same, added to |t - rint(t)|
+#endif
+#ifndef DMMT_QUANT_SCALED_HALF
+#define DMMT_QUANT_SCALED_HALF 0.49999905f  // 1/2 - 2^-20
+#endif
+// the unit check's view of which lanes were redone with the division
+#ifndef DMMT_QUANT_ON_REDO
+#define DMMT_QUANT_ON_REDO(r) ((void)0)
+#endif
 
 namespace dmmt {
 
 // quantizer.rs:60: round(d / q) half away from zero, Rust's saturating `as i16`
-__device__ __forceinline__ int16_t quantize(float d, float q) {
+DMMT_DQ_FN int16_t quantize(float d, float q) {
     float x = roundf(d / q);
     if (x != x) return 0;
     x = fminf(fmaxf(x, -32768.0f), 32767.0f);
@@ -24,13 +54,13 @@ __device__ __forceinline__ int16_t quantize(float d, float q) {
 // trunc(a + 0.5) there, exactly: a < 2^22 and a's fraction is farther than
 // a * 2^-20 > ulp(a + 0.5) / 2 from 1/2, so the addition cannot round across an
 // integer -- and the rare lanes outside it redone with the division afterwards.
-__device__ __forceinline__ void quantize_col8(const float (&v)[8], const float* q, const float* rq, int (&x)[8]) {
+DMMT_DQ_FN void quantize_col8(const float (&v)[8], const float* q, const float* rq, int (&x)[8]) {
     bool slow = false;
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
         const float t = v[r] * rq[8 * r];
         const float a = fabsf(t);
-        slow |= !(a < 4194304.0f && fabsf(__builtin_amdgcn_fractf(a) - 0.5f) > a * 0x1p-20f);
+        slow |= !(a < 4194304.0f && fabsf(DMMT_DQ_FRACT(a) - 0.5f) > a * DMMT_QUANT_F32_BAND);
         const float n = copysignf(fminf(truncf(a + 0.5f), 32768.0f), t);  // saturating `as i16` below
         x[r] = (int)fminf(n, 32767.0f);
     }
@@ -38,8 +68,10 @@ __device__ __forceinline__ void quantize_col8(const float (&v)[8], const float* 
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
             const float a = fabsf(v[r] * rq[8 * r]);
-            if (!(a < 4194304.0f && fabsf(__builtin_amdgcn_fractf(a) - 0.5f) > a * 0x1p-20f))
+            if (!(a < 4194304.0f && fabsf(DMMT_DQ_FRACT(a) - 0.5f) > a * DMMT_QUANT_F32_BAND)) {
+                DMMT_QUANT_ON_REDO(r);
                 x[r] = quantize(v[r], q[8 * r]);
+            }
         }
     }
 }
@@ -60,10 +92,14 @@ __device__ __forceinline__ void quantize_col8(const float (&v)[8], const float* 
 #define DMMT_S5 0.4499881f
 #define DMMT_S6 0.6532815f
 #define DMMT_S7 1.2814577f
+#ifdef __HIPCC__
 static __constant__ float c_arai_scale[8] = {DMMT_S0, DMMT_S1, DMMT_S2, DMMT_S3, DMMT_S4, DMMT_S5, DMMT_S6, DMMT_S7};
+#else
+static const float c_arai_scale[8] = {DMMT_S0, DMMT_S1, DMMT_S2, DMMT_S3, DMMT_S4, DMMT_S5, DMMT_S6, DMMT_S7};
+#endif
 
 // arai.rs:29-84: 8-point AAN butterfly, output k before its scaling factor
-__device__ __forceinline__ void arai8_unscaled(float (&v)[8]) {
+DMMT_DQ_FN void arai8_unscaled(float (&v)[8]) {
     const float v10 = v[0] + v[7], v11 = v[1] + v[6], v12 = v[2] + v[5], v13 = v[3] + v[4];
     const float v14 = v[3] - v[4], v15 = v[2] - v[5], v16 = v[1] - v[6], v17 = v[0] - v[7];
     const float v20 = v10 + v13, v21 = v11 + v12, v22 = v11 - v12, v23 = v10 - v13;
@@ -86,7 +122,7 @@ __device__ __forceinline__ void arai8_unscaled(float (&v)[8]) {
 }
 
 // arai.rs:29-92: the butterfly with its output scaling
-__device__ __forceinline__ void arai8(float (&v)[8]) {
+DMMT_DQ_FN void arai8(float (&v)[8]) {
     arai8_unscaled(v);
     v[0] = v[0] * DMMT_S0;
     v[1] = v[1] * DMMT_S1;
@@ -120,11 +156,11 @@ __device__ __forceinline__ void arai8(float (&v)[8]) {
 // The eight distances are folded with max before one compare; a NaN (only from
 // 0/0, maxval 0: `nan_possible`) would vanish in the max, so that case always
 // takes the exact path.
-__device__ __forceinline__ float quant_margin(float t, float n) {
-    return __builtin_fmaf(fabsf(t), 0x1p-21f, fabsf(t - n));  // (the product is exact: one rounding)
+DMMT_DQ_FN float quant_margin(float t, float n) {
+    return __builtin_fmaf(fabsf(t), DMMT_QUANT_SCALED_BAND, fabsf(t - n));  // (the product is exact: one rounding)
 }
-__device__ __forceinline__ void quantize_col8_scaled(const float (&u)[8], const float* q, const float* crq,
-                                                     bool nan_possible, int (&x)[8]) {
+DMMT_DQ_FN void quantize_col8_scaled(const float (&u)[8], const float* q, const float* crq, bool nan_possible,
+                                     int (&x)[8]) {
     float dist = 0.0f;
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
@@ -133,11 +169,14 @@ __device__ __forceinline__ void quantize_col8_scaled(const float (&u)[8], const 
         dist = fmaxf(dist, quant_margin(t, n));
         x[r] = (int)n;
     }
-    if (nan_possible || !(dist < 0.49999905f)) {  // 1/2 - 2^-20
+    if (nan_possible || !(dist < DMMT_QUANT_SCALED_HALF)) {
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
             const float t = u[r] * crq[8 * r];
-            if (!(quant_margin(t, __builtin_rintf(t)) < 0.49999905f)) x[r] = quantize(u[r] * c_arai_scale[r], q[8 * r]);
+            if (!(quant_margin(t, __builtin_rintf(t)) < DMMT_QUANT_SCALED_HALF)) {
+                DMMT_QUANT_ON_REDO(r);
+                x[r] = quantize(u[r] * c_arai_scale[r], q[8 * r]);
+            }
         }
     }
 }

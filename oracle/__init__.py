@@ -76,6 +76,8 @@ def lib():
         L.ref_subsample_resort.argtypes = [ctypes.POINTER(f32), i32, i32, i32, i32, i32, i32, ctypes.POINTER(f32)]
         L.ref_forward.restype = i32
         L.ref_forward.argtypes = [vp, i32, i32, i32, ctypes.POINTER(RefOptions), ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
+        L.ref_forward_dots.restype = i32
+        L.ref_forward_dots.argtypes = [vp, i32, i32, ctypes.POINTER(RefOptions), ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
         L.ref_encode_coefficients.restype = i32
         L.ref_encode_coefficients.argtypes = [vp, ctypes.c_size_t, i32, i32, ctypes.POINTER(RefOptions), ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
         L.ref_encode.restype = i32
@@ -158,6 +160,26 @@ def forward(rgb, maxval: int, preset: int, luma_q, chroma_q, threads: int = 1) -
     if rc != 0:
         raise OracleError(rc, "ref_forward")
     # (a copy through numpy: ctypes.string_at takes an int size, < 2 GiB)
+    arr = np.ctypeslib.as_array((ctypes.c_int16 * (n.value * 64)).from_address(out.value)).reshape(n.value, 64).copy()
+    L.ref_free(out)
+    return arr
+
+
+def forward_dots(dots, preset: int, luma_q, chroma_q) -> np.ndarray:
+    """Front half from Image<f32> dots: an HxWx3 float32 array as color.rs:45-53 leaves
+    it -- not normalised, not range-checked, any float (Inf, NaN, denormals).  The
+    blocks as `forward` returns them; forward(rgb, maxval) is forward_dots(rgb / maxval)."""
+    a = np.ascontiguousarray(np.asarray(dots), dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("dots must be HxWx3")
+    h, w, _ = a.shape
+    opt = make_options(preset, luma_q, chroma_q)
+    out = ctypes.c_void_p()
+    n = ctypes.c_size_t()
+    L = lib()
+    rc = L.ref_forward_dots(a.ctypes.data, w, h, ctypes.byref(opt), ctypes.byref(out), ctypes.byref(n))
+    if rc != 0:
+        raise OracleError(rc, "ref_forward_dots")
     arr = np.ctypeslib.as_array((ctypes.c_int16 * (n.value * 64)).from_address(out.value)).reshape(n.value, 64).copy()
     L.ref_free(out)
     return arr

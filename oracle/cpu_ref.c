@@ -572,9 +572,11 @@ static void* dct_worker(void* arg) {
 }
 
 /* Transformer::transform (transformer.rs:188-221) up to the quantised,
- * entangled blocks, then MCU interleave (block_fold_iterator.rs). */
-static int ref_forward_impl(const uint16_t* rgb, int width, int height, int maxval, const ref_options* opt,
-                            int n_threads, int16_t** coef_zz, size_t* nblocks) {
+ * entangled blocks, then MCU interleave (block_fold_iterator.rs), from the
+ * Image<f32> dots (R, G, B per pixel) as color.rs:45-53 left them: nothing is
+ * normalised or range-checked here, any float goes through. */
+static int forward_dots_impl(const float* dots, int width, int height, const ref_options* opt, int n_threads,
+                             int16_t** coef_zz, size_t* nblocks) {
     int hr = opt->preset == REF_P444 ? 1 : 2, vr = opt->preset == REF_P420 ? 2 : 1;
     if (width <= 0 || height <= 0) return REF_E_INVALID_ARGUMENT;
     /* padder.rs:12-17 with multiples (8*hr, 8*vr) (transformer.rs:48-51), u16 */
@@ -588,20 +590,15 @@ static int ref_forward_impl(const uint16_t* rgb, int width, int height, int maxv
     float* py = planes;
     float* pcb = planes + npx;
     float* pcr = planes + 2 * npx;
-    /* ppm.rs:153-157 (RangeColorFormat::new panics above max, color.rs:63-65),
-     * padder.rs:19-34 (black pad), color.rs:75-100, transformer.rs:65-85 */
+    /* padder.rs:19-34 (black pad: dots 0.0), color.rs:75-100, transformer.rs:65-85 */
     for (int y = 0; y < hp; ++y) {
         for (int x = 0; x < wp; ++x) {
             float r = 0.0f, g = 0.0f, b = 0.0f;
             if (x < width && y < height) {
-                const uint16_t* px = rgb + ((size_t)y * width + x) * 3;
-                if (px[0] > maxval || px[1] > maxval || px[2] > maxval) {
-                    free(planes);
-                    return REF_E_VALUE_EXCEEDS_MAX;
-                }
-                r = ref_normalize(px[0], (uint16_t)maxval);
-                g = ref_normalize(px[1], (uint16_t)maxval);
-                b = ref_normalize(px[2], (uint16_t)maxval);
+                const float* px = dots + ((size_t)y * width + x) * 3;
+                r = px[0];
+                g = px[1];
+                b = px[2];
             }
             float ycc[3];
             ref_rgb_to_ycbcr(r, g, b, ycc);
@@ -699,6 +696,35 @@ static int ref_forward_impl(const uint16_t* rgb, int width, int height, int maxv
     *coef_zz = out;
     *nblocks = nb;
     return REF_OK;
+}
+
+/* Integer samples: the range check and the normalisation (ppm.rs:153-157,
+ * RangeColorFormat::new panics above max, color.rs:63-65; color.rs:45-53), then
+ * the dots path above. */
+static int ref_forward_impl(const uint16_t* rgb, int width, int height, int maxval, const ref_options* opt,
+                            int n_threads, int16_t** coef_zz, size_t* nblocks) {
+    int hr = opt->preset == REF_P444 ? 1 : 2, vr = opt->preset == REF_P420 ? 2 : 1;
+    if (width <= 0 || height <= 0) return REF_E_INVALID_ARGUMENT;
+    if ((width + 8 * hr - 1) / (8 * hr) * (8 * hr) > 65535 || (height + 8 * vr - 1) / (8 * vr) * (8 * vr) > 65535)
+        return REF_E_INVALID_ARGUMENT; /* (before the range check, as the dots path has none) */
+    size_t n = (size_t)width * height * 3;
+    float* dots = (float*)malloc(sizeof(float) * n);
+    if (!dots) return REF_E_OOM;
+    for (size_t i = 0; i < n; ++i) {
+        if (rgb[i] > maxval) {
+            free(dots);
+            return REF_E_VALUE_EXCEEDS_MAX;
+        }
+        dots[i] = ref_normalize(rgb[i], (uint16_t)maxval);
+    }
+    int rc = forward_dots_impl(dots, width, height, opt, n_threads, coef_zz, nblocks);
+    free(dots);
+    return rc;
+}
+
+int ref_forward_dots(const float* dots, int width, int height, const ref_options* opt, int16_t** coef_zz,
+                     size_t* nblocks) {
+    return forward_dots_impl(dots, width, height, opt, 1, coef_zz, nblocks);
 }
 
 /* ------------------------------------------------------------ parallel front half

@@ -70,6 +70,11 @@ void ref_subsample_resort(const float* plane, int w, int h, int hr, int vr, int 
 /* Front half: padded image -> quantized blocks, zigzag order, MCU emission order. */
 int ref_forward(const uint16_t* rgb, int width, int height, int maxval, const ref_options* opt,
                 int16_t** coef_zz, size_t* nblocks);
+/* The same from Image<f32> dots (width*height*3 floats, R G B per pixel, as
+ * color.rs:45-53 leaves them): not normalised, not range-checked, any float.
+ * ref_forward is the range check and the normalisation, then this. */
+int ref_forward_dots(const float* dots, int width, int height, const ref_options* opt, int16_t** coef_zz,
+                     size_t* nblocks);
 /* Back half: emission-order zigzag blocks -> complete JPEG file. */
 int ref_encode_coefficients(const int16_t* coef_zz, size_t nblocks, int width, int height,
                             const ref_options* opt, uint8_t** out, size_t* out_len);

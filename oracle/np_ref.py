@@ -2,8 +2,9 @@
 
 numpy float32 for the front half (every ufunc rounds once, no contraction),
 pure Python integers for the back half.  Written separately from cpu_ref.c so
-the two restatements cross-check each other (tests/test_oracle_crosscheck.py);
-only tests import it.  Citations are reference file:line.
+the two restatements cross-check each other (tests/test_oracle_golden.py on
+integer samples, tests/test_oracle_dots.py on float dots); only tests import it.
+Citations are reference file:line.
 """
 from __future__ import annotations
 
@@ -85,18 +86,46 @@ def to_blocks(plane):
     return plane.reshape(h // 8, 8, w // 8, 8).transpose(0, 2, 1, 3).reshape(-1, 8, 8)
 
 
-def forward(rgb, maxval, preset, luma_q, chroma_q):
-    """Front half -> (nblocks, 64) int16 zigzag blocks in MCU emission order."""
-    rgb = np.asarray(rgb)
-    h, w, _ = rgb.shape
+def emission_order(n_mcu, line, preset):
+    """block_fold_iterator.rs:53-148 as indices: per MCU its luma blocks (indices into
+    the luma plane's block raster, `line` blocks per block row), then Cb m, then Cr m.
+    Returns (luma index array (n_mcu, n_luma), n_luma)."""
+    hr = 1 if preset == 0 else 2
+    cbx = line // hr
+    m = np.arange(n_mcu)
+    mx, my = m % cbx, m // cbx
+    if preset == 0:
+        ys = [m]
+    elif preset == 1:
+        ys = [my * line + 2 * mx, my * line + 2 * mx + 1]
+    else:
+        r0 = 2 * my * line
+        ys = [r0 + 2 * mx, r0 + 2 * mx + 1, r0 + line + 2 * mx, r0 + line + 2 * mx + 1]
+    return np.stack(ys, axis=1), len(ys)
+
+
+def interleave(yb, cbb, crb, preset, line):
+    """per-plane blocks (n, ...) of any dtype -> the blocks in MCU emission order"""
+    ys, n_luma = emission_order(cbb.shape[0], line, preset)
+    out = np.empty((cbb.shape[0], n_luma + 2) + yb.shape[1:], yb.dtype)
+    out[:, :n_luma] = yb[ys]
+    out[:, n_luma] = cbb
+    out[:, n_luma + 1] = crb
+    return out.reshape((-1,) + yb.shape[1:])
+
+
+def forward_dct(dots, preset):
+    """Image<f32> dots (HxWx3 float32, as color.rs:45-53 leaves them: not normalised,
+    not range-checked) -> the float32 coefficients before quantisation: the (n, 8, 8)
+    blocks of the Y, Cb and Cr planes in block raster order, and the padded width."""
+    dots = np.asarray(dots, dtype=np.float32)
+    h, w, _ = dots.shape
     hr = 1 if preset == 0 else 2
     vr = 2 if preset == 2 else 1
     wp = -(-w // (8 * hr)) * 8 * hr
     hp = -(-h // (8 * vr)) * 8 * vr
-    norm = rgb.astype(np.float32) / f32(maxval)
     padded = np.zeros((hp, wp, 3), np.float32)
-    padded[:h, :w] = norm
-    y, cb, cr = rgb_to_ycbcr(padded[..., 0], padded[..., 1], padded[..., 2])
+    padded[:h, :w] = dots
 
     def sub(p):
         if preset == 0:
@@ -106,26 +135,25 @@ def forward(rgb, maxval, preset, luma_q, chroma_q):
         # rect 2x2, x outer / y inner: (x,y) (x,y+1) (x+1,y) (x+1,y+1)
         return (((p[0::2, 0::2] + p[1::2, 0::2]) + p[0::2, 1::2]) + p[1::2, 1::2]) / f32(4.0)
 
-    yb = quantize(dct_blocks(to_blocks(y)), luma_q).reshape(-1, 64)
-    cbb = quantize(dct_blocks(to_blocks(sub(cb))), chroma_q).reshape(-1, 64)
-    crb = quantize(dct_blocks(to_blocks(sub(cr))), chroma_q).reshape(-1, 64)
-    line = wp // 8
-    cbx = wp // hr // 8
-    out = []
-    for m in range(cbb.shape[0]):
-        mx, my = m % cbx, m // cbx
-        if preset == 0:
-            ys = [m]
-        elif preset == 1:
-            ys = [my * line + 2 * mx, my * line + 2 * mx + 1]
-        else:
-            r0 = 2 * my * line
-            ys = [r0 + 2 * mx, r0 + 2 * mx + 1, r0 + line + 2 * mx, r0 + line + 2 * mx + 1]
-        out.extend(yb[i] for i in ys)
-        out.append(cbb[m])
-        out.append(crb[m])
-    blocks = np.stack(out)
-    return blocks[:, ZIGZAG]
+    with np.errstate(all="ignore"):  # Inf and NaN dots are inputs like any other
+        y, cb, cr = rgb_to_ycbcr(padded[..., 0], padded[..., 1], padded[..., 2])
+        return (dct_blocks(to_blocks(y)), dct_blocks(to_blocks(sub(cb))), dct_blocks(to_blocks(sub(cr))), wp)
+
+
+def forward_dots(dots, preset, luma_q, chroma_q):
+    """Front half from Image<f32> dots -> (nblocks, 64) int16 zigzag blocks in MCU
+    emission order."""
+    yc, cbc, crc, wp = forward_dct(dots, preset)
+    with np.errstate(all="ignore"):
+        yb = quantize(yc, luma_q).reshape(-1, 64)
+        cbb = quantize(cbc, chroma_q).reshape(-1, 64)
+        crb = quantize(crc, chroma_q).reshape(-1, 64)
+    return interleave(yb, cbb, crb, preset, wp // 8)[:, ZIGZAG]
+
+
+def forward(rgb, maxval, preset, luma_q, chroma_q):
+    """Integer samples: normalise (color.rs:45-53), then the dots path."""
+    return forward_dots(np.asarray(rgb).astype(np.float32) / f32(maxval), preset, luma_q, chroma_q)
 
 
 # ------------------------------------------------------------------ back half

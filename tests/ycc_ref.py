@@ -55,29 +55,21 @@ def padded_planes(y, cb, cr, sub):
     return out
 
 
+def forward_dct(y, cb, cr, sub):
+    """the float32 coefficients before quantisation: the (n, 8, 8) blocks of the Y, Cb
+    and Cr planes in block raster order, and the padded luma width"""
+    yp, cbp, crp = padded_planes(y, cb, cr, sub)
+    return (np_ref.dct_blocks(np_ref.to_blocks(yp)), np_ref.dct_blocks(np_ref.to_blocks(cbp)),
+            np_ref.dct_blocks(np_ref.to_blocks(crp)), yp.shape[1])
+
+
 def coefficients(y, cb, cr, sub, luma_q, chroma_q):
     """(nblocks, 64) int16 zigzag blocks in MCU emission order, interleaved as np_ref.forward does"""
-    yp, cbp, crp = padded_planes(y, cb, cr, sub)
-    yb = np_ref.quantize(np_ref.dct_blocks(np_ref.to_blocks(yp)), luma_q).reshape(-1, 64)
-    cbb = np_ref.quantize(np_ref.dct_blocks(np_ref.to_blocks(cbp)), chroma_q).reshape(-1, 64)
-    crb = np_ref.quantize(np_ref.dct_blocks(np_ref.to_blocks(crp)), chroma_q).reshape(-1, 64)
-    hr, _ = rates(sub)
-    line = yp.shape[1] // 8
-    cbx = line // hr
-    out = []
-    for m in range(cbb.shape[0]):
-        mx, my = m % cbx, m // cbx
-        if sub == 0:
-            ys = [m]
-        elif sub == 1:
-            ys = [my * line + 2 * mx, my * line + 2 * mx + 1]
-        else:
-            r0 = 2 * my * line
-            ys = [r0 + 2 * mx, r0 + 2 * mx + 1, r0 + line + 2 * mx, r0 + line + 2 * mx + 1]
-        out.extend(yb[i] for i in ys)
-        out.append(cbb[m])
-        out.append(crb[m])
-    return np.stack(out)[:, np_ref.ZIGZAG]
+    yc, cbc, crc, wp = forward_dct(y, cb, cr, sub)
+    yb = np_ref.quantize(yc, luma_q).reshape(-1, 64)
+    cbb = np_ref.quantize(cbc, chroma_q).reshape(-1, 64)
+    crb = np_ref.quantize(crc, chroma_q).reshape(-1, 64)
+    return np_ref.interleave(yb, cbb, crb, sub, wp // 8)[:, np_ref.ZIGZAG]
 
 
 def encode(y, cb, cr, sub, luma_q, chroma_q, restart_interval=0) -> bytes:
