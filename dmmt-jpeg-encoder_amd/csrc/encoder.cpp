@@ -70,7 +70,7 @@ struct Lane {
     hipStream_t stream = nullptr;
     int* status = nullptr;   // [2][kStatusWords], host-mapped
     int* dstatus = nullptr;  // its device address
-    DevBuf coef, dcdiff, lastnz, ac_hist, dc_hist, code_tab, hdr_len, total_out, stage, chunk_bits, chunk_ff,
+    DevBuf coef, coef_lo, coef_hi, dcdiff, lastnz, ac_hist, dc_hist, code_tab, hdr_len, total_out, stage, chunk_bits, chunk_ff,
         chunk_ff8, chunk_edge, chunk_bit0, chunk_out, arrive;
     // dmmt_convert_ppm_device_batch: a file's samples and its comment-free decode state
     DevBuf ppm_rgb, ppm_counts, ppm_rowbase;
@@ -117,6 +117,9 @@ struct dmmt_ctx {
     // k_tables fused into k_hist's last workgroup where tables_fusable (DMMT_FUSE_TABLES=0: the
     // separate launch, for measurements)
     bool fuse_tables = DMMT_FUSE_TABLES_DEFAULT != 0;
+    // the form of the quantised blocks between k_front and the entropy kernels
+    // (coef_format.hpp; DMMT_COEF_FORMAT=auto|wide|narrow, for measurements and tests)
+    int coef_format = COEF_FORMAT_AUTO;
     std::vector<GraphEntry> graphs;
     uint64_t graph_clock = 0;
     // MCU-row stripe between dmmt_stripe_analyze and dmmt_stripe_encode
@@ -246,12 +249,16 @@ int upload_tables(dmmt_ctx* c, const dmmt_options* opt, int maxval, int sb, hipS
     return DMMT_OK;
 }
 
-int ensure_work(dmmt_ctx* c, const Geom& g, int nf, Work* w, int lane, bool async) {
+int ensure_work(dmmt_ctx* c, const Geom& g, int nf, Work* w, int lane, bool async, bool narrow = false) {
     int rc;
     Lane* L = c->lanes[lane];
     const size_t nb = (size_t)g.bpf * nf;
     const size_t nch = (size_t)g.nch * nf;
     if ((rc = ensure(L->coef, nb * 64 * sizeof(int16_t)))) return rc;
+    if (narrow) {  // (coef stays: the escape store)
+        if ((rc = ensure(L->coef_lo, nb * kCoefLoBytes))) return rc;
+        if ((rc = ensure(L->coef_hi, nb * kCoefHiBytes))) return rc;
+    }
     if ((rc = ensure(L->dcdiff, nb * sizeof(int16_t)))) return rc;
     if ((rc = ensure(L->lastnz, nb))) return rc;
     // staging slots sized for the worst case; k_stuffwrite reads up to 4 words
@@ -285,6 +292,8 @@ int ensure_work(dmmt_ctx* c, const Geom& g, int nf, Work* w, int lane, bool asyn
         }
     }
     w->coef = (int16_t*)L->coef.p;
+    w->coef_lo = narrow ? (int16_t*)L->coef_lo.p : nullptr;
+    w->coef_hi = narrow ? (int8_t*)L->coef_hi.p : nullptr;
     w->dcdiff = (int16_t*)L->dcdiff.p;
     w->lastnz = (uint8_t*)L->lastnz.p;
     w->ac_hist = (uint32_t*)L->ac_hist.p;
@@ -309,9 +318,12 @@ int ensure_work(dmmt_ctx* c, const Geom& g, int nf, Work* w, int lane, bool asyn
 
 // workspace + tables for one launch batch; every table pointer is valid on return
 int prepare(dmmt_ctx* c, const Geom& g, int nf, const dmmt_options* opt, int sb, hipStream_t st, Work* w,
-            int lane = 0, bool async = false, int* status = nullptr) {
+            int lane = 0, bool async = false, int* status = nullptr, bool allow_narrow = false) {
     int rc;
-    if ((rc = ensure_work(c, g, nf, w, lane, async))) return rc;
+    // (allow_narrow: the caller's front end is a k_front kernel and nothing but the
+    // entropy kernels reads the blocks after it)
+    const bool narrow = allow_narrow && coef_narrow_for(c->coef_format, sb, opt->luma_q, opt->chroma_q);
+    if ((rc = ensure_work(c, g, nf, w, lane, async, narrow))) return rc;
     if (status) w->status = status;  // (a per-file status area of dmmt_convert_ppm_device_batch)
     if ((rc = upload_tables(c, opt, g.maxval, sb, st))) return rc;
     w->norm_lut = (const float*)c->lut.p;
@@ -431,7 +443,7 @@ int enqueue_encode(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, 
                    const YccFrames* yf = nullptr) {
     Work w;
     int rc;
-    if ((rc = prepare(c, g, nf, opt, sb, st, &w, lane, async, status))) return rc;
+    if ((rc = prepare(c, g, nf, opt, sb, st, &w, lane, async, status, true))) return rc;
     const int bits = opt->bits_per_channel;
     // (a per-file status area -- dmmt_convert_ppm_device_batch -- would put a new
     // pointer into every file's graph key: that path launches directly)
@@ -533,7 +545,7 @@ dmmt_ctx* primary(dmmt_ctx* c) { return c && c->group ? group_member(c->group, 0
 void destroy_lane(Lane* L, bool own_stream) {
     (void)hipStreamSynchronize(L->stream);
     if (L->status) (void)hipHostFree(L->status);
-    DevBuf* bufs[] = {&L->coef,      &L->dcdiff,     &L->lastnz,     &L->ac_hist,
+    DevBuf* bufs[] = {&L->coef,      &L->coef_lo,    &L->coef_hi,    &L->dcdiff,     &L->lastnz,     &L->ac_hist,
                       &L->dc_hist,  &L->code_tab,  &L->hdr_len,    &L->total_out,  &L->stage,
                       &L->chunk_bits, &L->chunk_ff, &L->chunk_ff8, &L->chunk_edge, &L->chunk_bit0, &L->chunk_out,
                       &L->arrive,     &L->ppm_rgb,    &L->ppm_counts, &L->ppm_rowbase};
@@ -567,6 +579,8 @@ extern "C" int dmmt_ctx_create(int device, dmmt_ctx** out) {
     c->device = device;
     if (const char* e = getenv("DMMT_GRAPHS")) c->use_graphs = atoi(e) != 0;
     if (const char* e = getenv("DMMT_FUSE_TABLES")) c->fuse_tables = atoi(e) != 0;
+    if (const char* e = getenv("DMMT_COEF_FORMAT"))
+        c->coef_format = !strcmp(e, "wide") ? COEF_FORMAT_WIDE : !strcmp(e, "narrow") ? COEF_FORMAT_NARROW : COEF_FORMAT_AUTO;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
         delete c;
         return DMMT_E_HIP;
@@ -598,7 +612,7 @@ int ctx_check_device(dmmt_ctx* c) {
     if ((rc = set_device(c))) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     for (Lane* L : c->lanes) {
-        const DevBuf* bufs[] = {&L->coef,       &L->dcdiff,   &L->lastnz,     &L->ac_hist,    &L->dc_hist,
+        const DevBuf* bufs[] = {&L->coef,       &L->coef_lo,  &L->coef_hi,    &L->dcdiff,   &L->lastnz,     &L->ac_hist,    &L->dc_hist,
                                 &L->code_tab,   &L->hdr_len,  &L->total_out,  &L->stage,      &L->chunk_bits,
                                 &L->chunk_ff,   &L->chunk_ff8,  &L->chunk_edge, &L->chunk_bit0, &L->chunk_out, &L->arrive,
                                 &L->ppm_rgb,    &L->ppm_counts, &L->ppm_rowbase};
@@ -1555,7 +1569,7 @@ extern "C" int dmmt_stripe_analyze(dmmt_ctx* c, const dmmt_stripe* st, const dmm
     if ((rc = set_device(c))) return rc;
     hipStream_t s = c->stream;
     Work w;
-    if ((rc = prepare(c, g, 1, opt, st->sample_bytes, s, &w))) return rc;
+    if ((rc = prepare(c, g, 1, opt, st->sample_bytes, s, &w, 0, false, nullptr, true))) return rc;
     {
         StageTimer t(c, ST_FRONT, s);
         HIP_TRY(launch_front(st->d_rgb, (size_t)st->width * g.height * 3 * st->sample_bytes, st->sample_bytes, 1, g, w,
@@ -1585,18 +1599,21 @@ extern "C" int dmmt_stripe_analyze(dmmt_ctx* c, const dmmt_stripe* st, const dmm
         }
     }
     if (g.restart_interval == 0) {  // joined stripes: DC edges for the neighbours' predictors
-        // the DCs are index 0 of the (column-major) blocks: the first and last MCU
-        std::vector<int16_t> head((size_t)g.bpm * 64), tail((size_t)g.bpm * 64);
+        // the DCs are index 0 of the (column-major) blocks, or of their lo records
+        // in the narrow form (bs int16 apart): the first and last MCU
+        const int16_t* const blocks = w.coef_lo ? w.coef_lo : w.coef;
+        const size_t bs = w.coef_lo ? kCoefLoCount : 64;
+        std::vector<int16_t> head((size_t)g.bpm * bs), tail((size_t)g.bpm * bs);
         const int nl = g.n_luma;
-        HIP_TRY(hipMemcpyAsync(head.data(), w.coef, head.size() * 2, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(tail.data(), w.coef + (g.bpf - g.bpm) * 64, tail.size() * 2, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(head.data(), blocks, head.size() * 2, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(tail.data(), blocks + (g.bpf - g.bpm) * bs, tail.size() * 2, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         c->stripe_dc_first[0] = head[0];  // the stripe's first Y, Cb, Cr blocks (emission order)
-        c->stripe_dc_first[1] = head[(size_t)nl * 64];
-        c->stripe_dc_first[2] = head[(size_t)(nl + 1) * 64];
-        c->stripe_dc_last[0] = tail[(size_t)(nl - 1) * 64];  // and its last ones
-        c->stripe_dc_last[1] = tail[(size_t)nl * 64];
-        c->stripe_dc_last[2] = tail[(size_t)(nl + 1) * 64];
+        c->stripe_dc_first[1] = head[(size_t)nl * bs];
+        c->stripe_dc_first[2] = head[(size_t)(nl + 1) * bs];
+        c->stripe_dc_last[0] = tail[(size_t)(nl - 1) * bs];  // and its last ones
+        c->stripe_dc_last[1] = tail[(size_t)nl * bs];
+        c->stripe_dc_last[2] = tail[(size_t)(nl + 1) * bs];
     }
     c->stripe_g = g;
     c->stripe_opt = *opt;
@@ -1674,7 +1691,7 @@ extern "C" int dmmt_stripe_measure(dmmt_ctx* c, const uint64_t hist_sum[DMMT_STR
     if (out_cap < max_jpeg_bytes(g)) return DMMT_E_CAPACITY;
     hipStream_t s = c->stream;
     Work w;
-    if ((rc = prepare(c, g, 1, &c->stripe_opt, c->stripe_sb, s, &w))) return rc;
+    if ((rc = prepare(c, g, 1, &c->stripe_opt, c->stripe_sb, s, &w, 0, false, nullptr, true))) return rc;
     if ((rc = upload_hist_sum(w, hist_sum, s))) return rc;
     // the stripe's first DC differences continue the previous stripe's predictors
     int16_t d[3];
@@ -1730,7 +1747,7 @@ extern "C" int dmmt_stripe_write(dmmt_ctx* c, uint64_t bit_offset, uint32_t next
     g.next16 = g.more_after ? (next16 & 0xFFFFu) & ~(0xFFFFu >> next_bits) : 0u;
     hipStream_t s = c->stream;
     Work w;
-    if ((rc = prepare(c, g, 1, &c->stripe_opt, c->stripe_sb, s, &w))) return rc;
+    if ((rc = prepare(c, g, 1, &c->stripe_opt, c->stripe_sb, s, &w, 0, false, nullptr, true))) return rc;
     if ((rc = ensure(c->out_len, 4))) return rc;
     {
         StageTimer t(c, ST_OFFSETS, s);
@@ -1763,7 +1780,7 @@ extern "C" int dmmt_stripe_encode(dmmt_ctx* c, const uint64_t hist_sum[DMMT_STRI
     if (out_cap < max_jpeg_bytes(g)) return DMMT_E_CAPACITY;
     hipStream_t s = c->stream;
     Work w;
-    if ((rc = prepare(c, g, 1, &c->stripe_opt, c->stripe_sb, s, &w))) return rc;
+    if ((rc = prepare(c, g, 1, &c->stripe_opt, c->stripe_sb, s, &w, 0, false, nullptr, true))) return rc;
     // the summed histograms go into replica 0 (the other replicas are zero)
     if ((rc = upload_hist_sum(w, hist_sum, s))) return rc;
     if ((rc = ensure(c->out_len, 4))) return rc;

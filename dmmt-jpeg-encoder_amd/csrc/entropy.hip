@@ -177,9 +177,37 @@ __device__ __forceinline__ void zigzag_in_registers(BlockCoef& b) {
 // category its symbol carries (its low 4 bits; a DC symbol is the category): the
 // code shifted left by cat and the length plus cat, so a piece is the entry ORed
 // with the cat extra bits (ZRL and EOB have category 0).
-template <typename Sink>
-__device__ __forceinline__ void walk_block(const BlockCoef& b, int dcd, const uint2* __restrict__ dctab,
-                                           const uint2* __restrict__ actab, Sink& sink, int kmax = 63) {
+// The walk's view of zigzag position k (a constant once unrolled) of a wide block:
+// the non-zero test, one compare, and the value.
+__device__ __forceinline__ bool walk_nonzero(const BlockCoef& b, int k, uint32_t m_low) {
+    const int kc = DMMT_WALK_COLUMN_MAJOR ? coef_pos(k) : k;  // the coefficient's half-word
+    const uint32_t w = b.w[kc >> 1];
+    return (kc & 1) ? w > m_low : (w << 16) != 0u;
+}
+__device__ __forceinline__ int walk_value(const BlockCoef& b, int k) {
+    return coef_at(b, DMMT_WALK_COLUMN_MAJOR ? coef_pos(k) : k);
+}
+// ... and of a narrow one (coef_format.hpp): a half-word of the lo words below
+// position 8, else a byte of the hi words (an escape reads -128)
+__device__ __forceinline__ bool walk_nonzero(const NarrowCoef& b, int k, uint32_t m_low) {
+    if (coef_in_lo(k)) {
+        const uint32_t w = b.lo[k >> 1];
+        return (k & 1) ? w > m_low : (w << 16) != 0u;
+    }
+    const uint32_t w = b.hi[coef_hi_word(k)];
+    const int s = coef_hi_shift(k);
+    return s == 24 ? w > 0x00FFFFFFu : s == 0 ? (w << 24) != 0u : (w & (0xFFu << s)) != 0u;
+}
+__device__ __forceinline__ int walk_value(const NarrowCoef& b, int k) { return narrow_at(b, k); }
+
+// esc (narrow blocks): the block in the wide store, read where a hi byte is an
+// escape -- one vote per non-zero position, like the ZRL vote.  ESC = false: the
+// walk of a wave without a flagged block (narrow_flag), no escape test
+template <bool ESC = true, typename Sink, typename Block>
+__device__ __forceinline__ void walk_block(const Block& b, int dcd, const uint2* __restrict__ dctab,
+                                           const uint2* __restrict__ actab, Sink& sink, int kmax = 63,
+                                           const int16_t* esc = nullptr) {
+    constexpr bool kNarrow = std::is_same<Block, NarrowCoef>::value;
     {
         const int cat = category_of(dcd);
         const uint2 e = dctab[cat];
@@ -201,10 +229,13 @@ __device__ __forceinline__ void walk_block(const BlockCoef& b, int dcd, const ui
         if (k0 != 0 && k0 > kmax) break;
 #pragma unroll
         for (int k = k0 ? k0 : 1; k < k0 + 4; ++k) {
-            const int kc =DMMT_WALK_COLUMN_MAJOR ? coef_pos(k) : k;  // the coefficient's half-word
-            const uint32_t w = b.w[kc >> 1];
-            if ((kc & 1) ? w > m_low : (w << 16) != 0u) {
-                const int v = coef_at(b, kc);
+            if (walk_nonzero(b, k, m_low)) {
+                int v = walk_value(b, k);
+                if (kNarrow && ESC && !coef_in_lo(k)) {
+                    if (__builtin_amdgcn_ballot_w64(v == kCoefEscape) != 0) {  // rare
+                        if (v == kCoefEscape) v = (int)esc[coef_pos(k)];
+                    }
+                }
                 const int r16 = 16 * k - l16;
                 // a run of 16 or more (from position 17 on: l16 >= 16), rare: one vote
                 // and a scalar branch for the wave, not a second exec-mask region
@@ -354,10 +385,13 @@ __device__ __forceinline__ int tid_again(int wave) {
 // fuse: the frame's last workgroup to finish also computes every chunk's offsets
 // (fused_offsets; `arrive` counts the finished workgroups per frame and is zero
 // between launches), so no k_offsets launch follows
-template <int OCC>
-__global__ __launch_bounds__(kEmitThreads, OCC) void k_emit(const int16_t* coef, const int16_t* __restrict__ dcdiff,
+// NARROW (k_emit_n): the blocks come in the 80-byte form (coef_lo, coef_hi; coef
+// the escape store): 20 registers a block instead of 32.
+template <bool NARROW>
+__device__ __forceinline__ void emit_body(const int16_t* coef, const int16_t* __restrict__ coef_lo,
+                                              const int8_t* __restrict__ coef_hi, const int16_t* __restrict__ dcdiff,
                                               const uint8_t* __restrict__ lastnz,
-                                              const uint32_t* __restrict__ code_tab, Geom g,
+                                              const uint32_t* __restrict__ code_tab, const Geom& g,
                                               uint32_t* __restrict__ stage, uint32_t* __restrict__ chunk_bits,
                                               uint32_t* __restrict__ chunk_ff, uint32_t* __restrict__ chunk_edge,
                                               uint32_t* __restrict__ ac_hist, uint32_t* __restrict__ dc_hist,
@@ -469,9 +503,13 @@ __global__ __launch_bounds__(kEmitThreads, OCC) void k_emit(const int16_t* coef,
         if (valid) {
             const int p = sOrder[tid];
             const long long ep = (long long)frame * g.bpf + el0 + p;
-            BlockCoef b;
-            load_block(coef + ep * 64, b);
-            zigzag_in_registers(b);
+            std::conditional_t<NARROW, NarrowCoef, BlockCoef> b;
+            if constexpr (NARROW) {
+                load_narrow(coef_lo, coef_hi, ep, b);
+            } else {
+                load_block(coef + ep * 64, b);
+                zigzag_in_registers(b);
+            }
             const int dp = dcdiff[ep];
             DMMT_TRACE(4);
             const int kp = mod_small(r0 + p, g.bpm, inv16);
@@ -479,7 +517,14 @@ __global__ __launch_bounds__(kEmitThreads, OCC) void k_emit(const int16_t* coef,
             // the wave's walk stops after the last position any of its blocks uses
             const int kmax = __builtin_amdgcn_readfirstlane((int)sKey[min(64 * wave + 63, nb - 1)]);
             SlotSink ss{sSlot + tid, 0ull, 0, 0};
-            walk_block(b, dp, sTab + 512 + (lum ? 0 : 16), sTab + (lum ? 0 : 256), ss, kmax);
+            if constexpr (NARROW) {
+                if (__builtin_amdgcn_ballot_w64(narrow_flag(b)) != 0)  // (uniform) rare: a block of the wave escapes
+                    walk_block<true>(b, dp, sTab + 512 + (lum ? 0 : 16), sTab + (lum ? 0 : 256), ss, kmax, coef + ep * 64);
+                else
+                    walk_block<false>(b, dp, sTab + 512 + (lum ? 0 : 16), sTab + (lum ? 0 : 256), ss, kmax);
+            } else {
+                walk_block(b, dp, sTab + 512 + (lum ? 0 : 16), sTab + (lum ? 0 : 256), ss, kmax);
+            }
             wbits = ss.finish();
             slot_over = wbits > (uint32_t)kSlotWords * 32u;
             // (with the walker's column in the high half: the block's thread finds its
@@ -581,11 +626,15 @@ __global__ __launch_bounds__(kEmitThreads, OCC) void k_emit(const int16_t* coef,
                 // the block again (L2 / MALL) and a second walk straight into the
                 // window: holding it in registers across the scan would halve the
                 // occupancy of this kernel
-                BlockCoef b;
-                load_block(coef + e * 64, b);
-                zigzag_in_registers(b);
+                std::conditional_t<NARROW, NarrowCoef, BlockCoef> b;
+                if constexpr (NARROW) {
+                    load_narrow(coef_lo, coef_hi, e, b);
+                } else {
+                    load_block(coef + e * 64, b);
+                    zigzag_in_registers(b);
+                }
                 WindowSink ws{sW, w0, wn + 1, 0ull, (int)(st & 31), (int)(st >> 5), true};
-                walk_block(b, dcdiff[e], sTab + 512 + (lum_t ? 0 : 16), sTab + (lum_t ? 0 : 256), ws);
+                walk_block(b, dcdiff[e], sTab + 512 + (lum_t ? 0 : 16), sTab + (lum_t ? 0 : 256), ws, 63, coef + e * 64);
                 ws.finish();
             }
             tid = tid_again(wave);
@@ -646,6 +695,38 @@ __global__ __launch_bounds__(kEmitThreads, OCC) void k_emit(const int16_t* coef,
     }
     DMMT_TRACE(3);
     DMMT_TRACE_FLUSH(0, 0);
+}
+
+template <int OCC>
+__global__ __launch_bounds__(kEmitThreads, OCC) void k_emit(const int16_t* coef, const int16_t* __restrict__ dcdiff,
+                                              const uint8_t* __restrict__ lastnz,
+                                              const uint32_t* __restrict__ code_tab, Geom g,
+                                              uint32_t* __restrict__ stage, uint32_t* __restrict__ chunk_bits,
+                                              uint32_t* __restrict__ chunk_ff, uint32_t* __restrict__ chunk_edge,
+                                              uint32_t* __restrict__ ac_hist, uint32_t* __restrict__ dc_hist,
+                                              int fuse, uint32_t* __restrict__ arrive,
+                                              unsigned long long* __restrict__ chunk_bit0,
+                                              unsigned long long* __restrict__ chunk_out,
+                                              unsigned long long* __restrict__ total_out,
+                                              unsigned long long* __restrict__ chunk_ff8, int prio) {
+    emit_body<false>(coef, nullptr, nullptr, dcdiff, lastnz, code_tab, g, stage, chunk_bits, chunk_ff, chunk_edge, ac_hist,
+                     dc_hist, fuse, arrive, chunk_bit0, chunk_out, total_out, chunk_ff8, prio);
+}
+template <int OCC>
+__global__ __launch_bounds__(kEmitThreads, OCC) void k_emit_n(const int16_t* coef, const int16_t* __restrict__ coef_lo,
+                                                const int8_t* __restrict__ coef_hi, const int16_t* __restrict__ dcdiff,
+                                                const uint8_t* __restrict__ lastnz,
+                                                const uint32_t* __restrict__ code_tab, Geom g,
+                                                uint32_t* __restrict__ stage, uint32_t* __restrict__ chunk_bits,
+                                                uint32_t* __restrict__ chunk_ff, uint32_t* __restrict__ chunk_edge,
+                                                uint32_t* __restrict__ ac_hist, uint32_t* __restrict__ dc_hist,
+                                                int fuse, uint32_t* __restrict__ arrive,
+                                                unsigned long long* __restrict__ chunk_bit0,
+                                                unsigned long long* __restrict__ chunk_out,
+                                                unsigned long long* __restrict__ total_out,
+                                                unsigned long long* __restrict__ chunk_ff8, int prio) {
+    emit_body<true>(coef, coef_lo, coef_hi, dcdiff, lastnz, code_tab, g, stage, chunk_bits, chunk_ff, chunk_edge, ac_hist,
+                    dc_hist, fuse, arrive, chunk_bit0, chunk_out, total_out, chunk_ff8, prio);
 }
 
 // The byte that starts m1 (1..7) bits before the end of a chunk: those last m1
@@ -1238,6 +1319,15 @@ hipError_t launch_emit(int n_frames, const Geom& g, const Work& w, bool fuse_off
     // eight: the eighth takes the last wave slot of every SIMD, and no other lane's
     // kernel runs beside it (1080p 4:2:0 x256, 4 lanes: -2.6 % with eight, level
     // with seven, profiles/r08_emit_occ8_ab.txt).
+    if (w.coef_lo) {
+        const auto kn = !prio && n_frames > 1 ? k_emit_n<kEmitOccBatch> : k_emit_n<kEmitOcc>;
+        hipLaunchKernelGGL(kn, dim3(g.nch, n_frames), dim3(kEmitThreads), 0, st, (const int16_t*)w.coef,
+                           (const int16_t*)w.coef_lo, (const int8_t*)w.coef_hi, (const int16_t*)w.dcdiff,
+                           (const uint8_t*)w.lastnz, (const uint32_t*)w.code_tab, g, w.stage, w.chunk_bits, w.chunk_ff,
+                           w.chunk_edge, w.ac_hist, w.dc_hist, fuse, w.arrive, w.chunk_bit0, w.chunk_out, w.total_out,
+                           w.chunk_ff8, prio || DMMT_EMIT_PRIO_ALWAYS ? 1 : 0);
+        return hipGetLastError();
+    }
     const auto kern = !prio && n_frames > 1 ? k_emit<kEmitOccBatch> : k_emit<kEmitOcc>;
     hipLaunchKernelGGL(kern, dim3(g.nch, n_frames), dim3(kEmitThreads), 0, st, (const int16_t*)w.coef,
                        (const int16_t*)w.dcdiff, (const uint8_t*)w.lastnz, (const uint32_t*)w.code_tab, g, w.stage, w.chunk_bits, w.chunk_ff,

@@ -85,10 +85,12 @@ __device__ __forceinline__ void lds_words(const uint8_t* s, int off, uint32_t (&
 //     can arise (nan_possible = false), and no sample can exceed a maxval: the
 //     kernel raises no status.
 // WPE: see front_ycc_wpe below.
-template <int HR, int VR, int FMT, int WPE>
-__global__ __launch_bounds__(256, WPE) void k_front_ycc(YccArgs ya, size_t frame_stride, Geom g,
-                                                       const float* __restrict__ qtab,  // [2][64] natural, as f32
-                                                       int16_t* __restrict__ coef) {
+// NARROW: the 80-byte block form (coef_format.hpp), as front_body's.
+template <int HR, int VR, int FMT, bool NARROW>
+__device__ __forceinline__ void front_ycc_body(const YccArgs& ya, size_t frame_stride, const Geom& g,
+                                               const float* __restrict__ qtab,  // [2][64] natural, as f32
+                                               int16_t* __restrict__ coef, int16_t* __restrict__ coef_lo,
+                                               int8_t* __restrict__ coef_hi) {
     constexpr bool NV = FMT != YCC_PLANAR;
     constexpr int VU = FMT == YCC_NV_VU ? 1 : 0;
     using T = YccTile<HR, VR, NV>;
@@ -236,7 +238,9 @@ __global__ __launch_bounds__(256, WPE) void k_front_ycc(YccArgs ya, size_t frame
                 el = (blk - NYB - CB) * BPM + NLUMA + 1;
             }
             const bool valid = el < nvalid;  // (uniform over the block's 8 lanes)
-            if (valid) {
+            if constexpr (NARROW) {
+                coef_store_column_narrow(x, col, el, valid, cbase, coef_lo + e0 * 8, coef_hi + e0 * 64);
+            } else if (valid) {
                 uint32_t pk[4];  // the low halves of two coefficients per word (one v_perm_b32)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) pk[i] = __builtin_amdgcn_perm((uint32_t)x[2 * i + 1], (uint32_t)x[2 * i], 0x05040100u);
@@ -244,6 +248,18 @@ __global__ __launch_bounds__(256, WPE) void k_front_ycc(YccArgs ya, size_t frame
             }
         }
     }
+}
+
+template <int HR, int VR, int FMT, int WPE>
+__global__ __launch_bounds__(256, WPE) void k_front_ycc(YccArgs ya, size_t frame_stride, Geom g,
+                                                       const float* __restrict__ qtab, int16_t* __restrict__ coef) {
+    front_ycc_body<HR, VR, FMT, false>(ya, frame_stride, g, qtab, coef, nullptr, nullptr);
+}
+template <int HR, int VR, int FMT, int WPE>
+__global__ __launch_bounds__(256, WPE) void k_front_ycc_n(YccArgs ya, size_t frame_stride, Geom g,
+                                                         const float* __restrict__ qtab, int16_t* __restrict__ coef,
+                                                         int16_t* __restrict__ coef_lo, int8_t* __restrict__ coef_hi) {
+    front_ycc_body<HR, VR, FMT, true>(ya, frame_stride, g, qtab, coef, coef_lo, coef_hi);
 }
 
 // ============================================================== launcher
@@ -260,6 +276,12 @@ static void front_ycc_impl(const YccArgs& ya, size_t frame_stride, int n_frames,
                            hipStream_t st, int per_cu_cap) {
     constexpr int TM = 32 / HR;
     const long long ntiles = (long long)((g.mcux + TM - 1) / TM) * g.mcuy;
+    if (w.coef_lo) {
+        static const FrontCfg cfgn = [] { return front_cfg(k_front_ycc_n<HR, VR, FMT, front_ycc_wpe()>); }();
+        hipLaunchKernelGGL((k_front_ycc_n<HR, VR, FMT, front_ycc_wpe()>), front_grid(cfgn, ntiles, n_frames, per_cu_cap),
+                           dim3(256), 0, st, ya, frame_stride, g, w.qtab, w.coef, w.coef_lo, w.coef_hi);
+        return;
+    }
     static const FrontCfg cfg = [] { return front_cfg(k_front_ycc<HR, VR, FMT, front_ycc_wpe()>); }();
     hipLaunchKernelGGL((k_front_ycc<HR, VR, FMT, front_ycc_wpe()>), front_grid(cfg, ntiles, n_frames, per_cu_cap),
                        dim3(256), 0, st, ya, frame_stride, g, w.qtab, w.coef);

@@ -278,11 +278,16 @@ struct SurfTile {
 // frames frame_stride bytes apart, through SurfTile, and phase A picks its three
 // samples at SPP-sample pixels of NPL planes (sa.bgr, wave-uniform: samples 0 and
 // 2 of an interleaved pixel change roles).
-template <int HR, int VR, typename Sample, int LAY>
+// NARROW: the blocks go out in the 80-byte form (coef_format.hpp: coef_lo, coef_hi,
+// coef the escape store); integer samples only.
+template <int HR, int VR, typename Sample, int LAY, bool NARROW = false>
 __device__ __forceinline__ void front_body(const Sample* __restrict__ rgb, size_t frame_stride, const SurfArgs& sa,
                                            Geom g, const float* __restrict__ norm_lut,
                                            const float* __restrict__ qtab,  // [2][64] natural, as f32
-                                           int16_t* __restrict__ coef, int* __restrict__ status) {
+                                           int16_t* __restrict__ coef, int* __restrict__ status,
+                                           int16_t* __restrict__ coef_lo = nullptr,
+                                           int8_t* __restrict__ coef_hi = nullptr) {
+    static_assert(!NARROW || sizeof(Sample) != 4, "Image<f32> dots are unbounded: wide blocks");
     constexpr int TM = 32 / HR;      // MCUs per tile
     constexpr int ROWS = 8 * VR;     // pixel rows per tile
     constexpr int NLUMA = HR * VR;
@@ -560,7 +565,9 @@ __device__ __forceinline__ void front_body(const Sample* __restrict__ rgb, size_
                 el = (blk - NYB - CB) * BPM + NLUMA + 1;
             }
             const bool valid = el < nvalid;  // (uniform over the block's 8 lanes)
-            if (valid) {
+            if constexpr (NARROW) {
+                coef_store_column_narrow(x, col, el, valid, cbase, coef_lo + e0 * 8, coef_hi + e0 * 64);
+            } else if (valid) {
                 uint32_t pk[4];  // the low halves of two coefficients per word (one v_perm_b32)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) pk[i] = __builtin_amdgcn_perm((uint32_t)x[2 * i + 1], (uint32_t)x[2 * i], 0x05040100u);
@@ -590,6 +597,24 @@ __global__ __launch_bounds__(256, WPE) void k_front_surf(SurfArgs sa, size_t fra
                                                     const float* __restrict__ qtab, int16_t* __restrict__ coef,
                                                     int* __restrict__ status) {
     front_body<HR, VR, Sample, LAY>(nullptr, frame_stride, sa, g, norm_lut, qtab, coef, status);
+}
+
+// the narrow twins (integer samples)
+template <int HR, int VR, typename Sample, int WPE>
+__global__ __launch_bounds__(256, WPE) void k_front_n(const Sample* __restrict__ rgb, size_t frame_stride, Geom g,
+                                                 const float* __restrict__ norm_lut, const float* __restrict__ qtab,
+                                                 int16_t* __restrict__ coef, int* __restrict__ status,
+                                                 int16_t* __restrict__ coef_lo, int8_t* __restrict__ coef_hi) {
+    front_body<HR, VR, Sample, LAY_TIGHT, true>(rgb, frame_stride, SurfArgs{}, g, norm_lut, qtab, coef, status, coef_lo,
+                                                coef_hi);
+}
+template <int HR, int VR, typename Sample, int LAY, int WPE>
+__global__ __launch_bounds__(256, WPE) void k_front_surf_n(SurfArgs sa, size_t frame_stride, Geom g,
+                                                      const float* __restrict__ norm_lut,
+                                                      const float* __restrict__ qtab, int16_t* __restrict__ coef,
+                                                      int* __restrict__ status, int16_t* __restrict__ coef_lo,
+                                                      int8_t* __restrict__ coef_hi) {
+    front_body<HR, VR, Sample, LAY, true>(nullptr, frame_stride, sa, g, norm_lut, qtab, coef, status, coef_lo, coef_hi);
 }
 
 // ============================================================== k_hist
@@ -627,15 +652,20 @@ constexpr int kTailLdsBytes = 7072;  // tables_tail's per-table regions (static_
 #ifndef DMMT_HIST_NEWEST_FIRST
 #define DMMT_HIST_NEWEST_FIRST 0  // study builds: 1 = every thread takes its passes in descending block order
 #endif
-template <bool CHECK, bool FUSE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_hist(const int16_t* __restrict__ coef, int16_t* __restrict__ dcdiff,
-                                              uint8_t* __restrict__ lastnz, Geom g,
-                                              uint32_t* __restrict__ ac_hist /*[frames][reps][2][256]*/,
-                                              uint32_t* __restrict__ dc_hist /*[frames][reps][2][16]*/,
-                                              int* __restrict__ status, uint32_t* __restrict__ arrive,
-                                              uint32_t* __restrict__ code_tab, uint8_t* __restrict__ out,
-                                              size_t out_stride, uint32_t* __restrict__ hdr_len,
-                                              const uint8_t* __restrict__ qtab_u8, int bits_per_channel) {
+// NARROW (k_hist_n): the blocks come in the 80-byte form (coef_format.hpp): one lo
+// and four hi loads, 20 registers; position kk >= 8 is a byte, and an escape byte
+// (a wave vote inside the non-zero branch) takes its int16 from coef.  The
+// -32768 test then lives at the lo positions and in that branch.
+template <bool CHECK, bool FUSE, bool NARROW>
+__device__ __forceinline__ void hist_body(const int16_t* __restrict__ coef, const int16_t* __restrict__ coef_lo,
+                                          const int8_t* __restrict__ coef_hi, int16_t* __restrict__ dcdiff,
+                                          uint8_t* __restrict__ lastnz, const Geom& g,
+                                          uint32_t* __restrict__ ac_hist /*[frames][reps][2][256]*/,
+                                          uint32_t* __restrict__ dc_hist /*[frames][reps][2][16]*/,
+                                          int* __restrict__ status, uint32_t* __restrict__ arrive,
+                                          uint32_t* __restrict__ code_tab, uint8_t* __restrict__ out,
+                                          size_t out_stride, uint32_t* __restrict__ hdr_len,
+                                          const uint8_t* __restrict__ qtab_u8, int bits_per_channel) {
     // four copies of the histograms (lane & 3): the lanes of a wave often count
     // the same symbol at the same position; 545 words apart (different banks).
     // FUSE: the same LDS then holds the tables' work (tables_tail).
@@ -678,12 +708,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     for (; el < bpf; el += stride) {
 #endif
         const long long e = base + el;
-        const uint4* q = reinterpret_cast<const uint4*>(coef + e * 64);
-        uint32_t cw[32];  // column-major (coef_pos)
+        uint32_t cw[NARROW ? 1 : 32];  // column-major (coef_pos)
+        NarrowCoef nc;
+        if constexpr (NARROW) {
+            load_narrow(coef_lo, coef_hi, e, nc);
+            cw[0] = nc.lo[0];
+        } else {
+            const uint4* q = reinterpret_cast<const uint4*>(coef + e * 64);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const uint4 v = q[i];
-            cw[4 * i] = v.x, cw[4 * i + 1] = v.y, cw[4 * i + 2] = v.z, cw[4 * i + 3] = v.w;
+            for (int i = 0; i < 8; ++i) {
+                const uint4 v = q[i];
+                cw[4 * i] = v.x, cw[4 * i + 1] = v.y, cw[4 * i + 2] = v.z, cw[4 * i + 3] = v.w;
+            }
         }
         const int t = k < (uint32_t)g.n_luma ? 0 : 1;
         // DC: the predictor is the previous block of the component, usually a few
@@ -698,31 +734,56 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         const int cur = (int)(int16_t)(cw[0] & 0xFFFFu);
         const int nb = __shfl_up(cur, (unsigned)back, 64);  // (lanes below `back` get their own)
         int pv = 0;
-        if (back) pv = lane >= back ? nb : (int)coef[(e - back) * 64];
+        if (back) pv = lane >= back ? nb : NARROW ? (int)coef_lo[(e - back) * 8] : (int)coef[(e - back) * 64];
         // AC: zigzag order in registers (a constant permutation of the 64 halves)
         HistCoef b;
+        if constexpr (!NARROW) {
 #pragma unroll
-        for (int j = 0; j < 32; ++j) {
-            const int i0 = coef_pos(2 * j), i1 = coef_pos(2 * j + 1);
-            const uint32_t lo = (cw[i0 >> 1] >> (16 * (i0 & 1))) & 0xFFFFu;
-            const uint32_t hi = (cw[i1 >> 1] >> (16 * (i1 & 1))) & 0xFFFFu;
-            b.w[j] = lo | (hi << 16);
+            for (int j = 0; j < 32; ++j) {
+                const int i0 = coef_pos(2 * j), i1 = coef_pos(2 * j + 1);
+                const uint32_t lo = (cw[i0 >> 1] >> (16 * (i0 & 1))) & 0xFFFFu;
+                const uint32_t hi = (cw[i1 >> 1] >> (16 * (i1 & 1))) & 0xFFFFu;
+                b.w[j] = lo | (hi << 16);
+            }
         }
         uint32_t* h = H + 256 * t;
         // l16 = 16 * (position of the last non-zero + 1): the zero run before position
         // kk is r16 / 16 with r16 = 16 * kk - l16, (run & 15) << 4 = r16 & 0xF0
         int l16 = 16;
         uint32_t zrl = 0;
+        // (narrow blocks: the escape test only in a wave that holds a flagged block)
+        auto walk = [&](auto with_escapes) {
+            constexpr bool ESC = decltype(with_escapes)::value;
 #pragma unroll
-        for (int kk = 1; kk < 64; ++kk) {
-            const int v = (kk & 1) ? ((int)b.w[kk >> 1] >> 16) : (int)(int16_t)(b.w[kk >> 1] & 0xFFFFu);
-            if (v != 0) {
-                if (CHECK && v == -32768) bad |= 4;
-                const int r16 = 16 * kk - l16;
-                zrl += (uint32_t)(r16 >> 8);
-                atomicAdd(&h[(r16 & 0xF0) | category_fast(v)], 1u);
-                l16 = 16 * kk + 16;
+            for (int kk = 1; kk < 64; ++kk) {
+                int v;
+                if constexpr (NARROW)
+                    v = narrow_at(nc, kk);
+                else
+                    v = (kk & 1) ? ((int)b.w[kk >> 1] >> 16) : (int)(int16_t)(b.w[kk >> 1] & 0xFFFFu);
+                if (v != 0) {
+                    if (NARROW && ESC && !coef_in_lo(kk)) {
+                        if (__builtin_amdgcn_ballot_w64(v == kCoefEscape) != 0) {  // rare: the int16 from the wide store
+                            if (v == kCoefEscape) v = (int)coef[e * 64 + coef_pos(kk)];
+                            if (CHECK && v == -32768) bad |= 4;
+                        }
+                    } else if (CHECK) {
+                        bad |= v == -32768 ? 4 : 0;
+                    }
+                    const int r16 = 16 * kk - l16;
+                    zrl += (uint32_t)(r16 >> 8);
+                    atomicAdd(&h[(r16 & 0xF0) | category_fast(v)], 1u);
+                    l16 = 16 * kk + 16;
+                }
             }
+        };
+        if constexpr (NARROW) {
+            if (__builtin_amdgcn_ballot_w64(narrow_flag(nc)) != 0)  // (uniform) rare: a block of the wave escapes
+                walk(std::integral_constant<bool, true>{});
+            else
+                walk(std::integral_constant<bool, false>{});
+        } else {
+            walk(std::integral_constant<bool, false>{});
         }
         if (zrl) atomicAdd(&h[0xF0], zrl);
         if (l16 < 16 * 64) atomicAdd(&h[0], 1u);  // EOB
@@ -770,6 +831,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                         qtab_u8, bits_per_channel, status, sSmall, sSmall + 4);
         }
     }
+}
+
+template <bool CHECK, bool FUSE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_hist(const int16_t* __restrict__ coef, int16_t* __restrict__ dcdiff,
+                                              uint8_t* __restrict__ lastnz, Geom g,
+                                              uint32_t* __restrict__ ac_hist, uint32_t* __restrict__ dc_hist,
+                                              int* __restrict__ status, uint32_t* __restrict__ arrive,
+                                              uint32_t* __restrict__ code_tab, uint8_t* __restrict__ out,
+                                              size_t out_stride, uint32_t* __restrict__ hdr_len,
+                                              const uint8_t* __restrict__ qtab_u8, int bits_per_channel) {
+    hist_body<CHECK, FUSE, false>(coef, nullptr, nullptr, dcdiff, lastnz, g, ac_hist, dc_hist, status, arrive, code_tab,
+                                  out, out_stride, hdr_len, qtab_u8, bits_per_channel);
+}
+template <bool CHECK, bool FUSE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_hist_n(const int16_t* __restrict__ coef, const int16_t* __restrict__ coef_lo,
+                                                const int8_t* __restrict__ coef_hi, int16_t* __restrict__ dcdiff,
+                                                uint8_t* __restrict__ lastnz, Geom g,
+                                                uint32_t* __restrict__ ac_hist, uint32_t* __restrict__ dc_hist,
+                                                int* __restrict__ status, uint32_t* __restrict__ arrive,
+                                                uint32_t* __restrict__ code_tab, uint8_t* __restrict__ out,
+                                                size_t out_stride, uint32_t* __restrict__ hdr_len,
+                                                const uint8_t* __restrict__ qtab_u8, int bits_per_channel) {
+    hist_body<CHECK, FUSE, true>(coef, coef_lo, coef_hi, dcdiff, lastnz, g, ac_hist, dc_hist, status, arrive, code_tab,
+                                 out, out_stride, hdr_len, qtab_u8, bits_per_channel);
 }
 
 // ============================================================== k_tables
@@ -1551,6 +1636,15 @@ static void front_impl(const void* rgb, size_t stride_elems, int n_frames, const
                        hipStream_t st, int per_cu_cap) {
     constexpr int TM = 32 / HR;
     const long long ntiles = (long long)((g.mcux + TM - 1) / TM) * g.mcuy;
+    if constexpr (sizeof(S) != 4) {
+        if (w.coef_lo) {
+            static const FrontCfg cfgn = [] { return front_cfg(k_front_n<HR, VR, S, front_wpe<HR, VR, S>()>); }();
+            hipLaunchKernelGGL((k_front_n<HR, VR, S, front_wpe<HR, VR, S>()>),
+                               front_grid(cfgn, ntiles, n_frames, per_cu_cap), dim3(256), 0, st, (const S*)rgb,
+                               stride_elems, g, w.norm_lut, w.qtab, w.coef, w.status, w.coef_lo, w.coef_hi);
+            return;
+        }
+    }
     static const FrontCfg cfg = [] { return front_cfg(k_front<HR, VR, S, front_wpe<HR, VR, S>()>); }();
     hipLaunchKernelGGL((k_front<HR, VR, S, front_wpe<HR, VR, S>()>), front_grid(cfg, ntiles, n_frames, per_cu_cap),
                        dim3(256), 0, st, (const S*)rgb, stride_elems, g, w.norm_lut, w.qtab, w.coef, w.status);
@@ -1561,6 +1655,15 @@ static void front_surf_impl(const SurfArgs& sa, size_t frame_stride, int n_frame
                             hipStream_t st, int per_cu_cap) {
     constexpr int TM = 32 / HR;
     const long long ntiles = (long long)((g.mcux + TM - 1) / TM) * g.mcuy;
+    if constexpr (sizeof(S) != 4) {
+        if (w.coef_lo) {
+            static const FrontCfg cfgn = [] { return front_cfg(k_front_surf_n<HR, VR, S, LAY, front_wpe<HR, VR, S>()>); }();
+            hipLaunchKernelGGL((k_front_surf_n<HR, VR, S, LAY, front_wpe<HR, VR, S>()>),
+                               front_grid(cfgn, ntiles, n_frames, per_cu_cap), dim3(256), 0, st, sa, frame_stride, g,
+                               w.norm_lut, w.qtab, w.coef, w.status, w.coef_lo, w.coef_hi);
+            return;
+        }
+    }
     static const FrontCfg cfg = [] { return front_cfg(k_front_surf<HR, VR, S, LAY, front_wpe<HR, VR, S>()>); }();
     hipLaunchKernelGGL((k_front_surf<HR, VR, S, LAY, front_wpe<HR, VR, S>()>),
                        front_grid(cfg, ntiles, n_frames, per_cu_cap), dim3(256), 0, st, sa, frame_stride, g, w.norm_lut,
@@ -1666,7 +1769,14 @@ hipError_t launch_hist(int n_frames, const Geom& g, const Work& w, int check_cat
                            w.dc_hist, w.status, w.arrive, w.code_tab, out, out_stride, w.hdr_len, w.qtab_u8,
                            bits_per_channel);
     };
-    if (check_cat)
+    auto gon = [&](auto kern) {
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, (const int16_t*)w.coef, (const int16_t*)w.coef_lo,
+                           (const int8_t*)w.coef_hi, w.dcdiff, w.lastnz, g, w.ac_hist, w.dc_hist, w.status, w.arrive,
+                           w.code_tab, out, out_stride, w.hdr_len, w.qtab_u8, bits_per_channel);
+    };
+    if (w.coef_lo)  // the narrow form: integer samples only, so no -32768 test
+        fuse ? gon(k_hist_n<false, true>) : gon(k_hist_n<false, false>);
+    else if (check_cat)
         fuse ? go(k_hist<true, true>) : go(k_hist<true, false>);
     else
         fuse ? go(k_hist<false, true>) : go(k_hist<false, false>);

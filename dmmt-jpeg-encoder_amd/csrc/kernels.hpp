@@ -3,13 +3,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "coef_format.hpp"
 #include "jpeg_common.hpp"
 
 namespace dmmt {
 
 // Device workspace of one launch batch (see the kernels for each buffer's role).
 struct Work {
-    int16_t* coef;                  // [frames][bpf][64] zigzag, emission order
+    int16_t* coef;                  // [frames][bpf][64] column-major blocks (coef_pos), emission order; narrow form: the escape store
+    int16_t* coef_lo;               // narrow form (coef_format.hpp): [frames][bpf][8], zigzag 0..7; nullptr: the call is wide
+    int8_t* coef_hi;                // narrow form: [frames][bpf][64] bytes at coef_pos
     int16_t* dcdiff;                // [frames][bpf]
     uint8_t* lastnz;                // [frames][bpf] zigzag position of the last non-zero AC (0: none)
     uint32_t* ac_hist;              // [frames][reps][2][256], zero between launches

@@ -26,7 +26,8 @@ for f in sorted(glob.glob(os.path.join(root, "p*", "run_counter_collection.csv")
 
 def short(name):
     n = name.split("(")[0].replace("void ", "").replace("dmmt::", "")
-    return n.split("<")[0]
+    n = n.split("<")[0]
+    return n[:-2] if n.endswith("_n") else n  # the narrow-form twin of a kernel (csrc/coef_format.hpp): the same stage
 
 
 kernels = {}
@@ -44,7 +45,8 @@ for name, cs in acc.items():
     if "fetch_bytes" in e and "write_bytes" in e:
         e["hbm_bytes"] = e["fetch_bytes"] + e["write_bytes"]
     for c in ("SQ_INSTS_VALU", "SQ_ACTIVE_INST_VALU", "SQ_BUSY_CYCLES", "SQ_WAVE_CYCLES", "SQ_WAIT_ANY",
-              "SQ_INSTS_SALU", "SQ_INSTS_LDS", "SQ_LDS_BANK_CONFLICT"):
+              "SQ_INSTS_SALU", "SQ_INSTS_LDS", "SQ_LDS_BANK_CONFLICT", "TCP_TCC_READ_REQ_sum", "TCC_HIT_sum",
+              "TCC_MISS_sum", "TA_BUSY_avr", "TCP_PENDING_STALL_CYCLES_sum"):
         if c in d:
             e[c] = d[c]
     kernels[k] = e
