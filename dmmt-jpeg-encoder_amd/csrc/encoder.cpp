@@ -1009,7 +1009,7 @@ extern "C" int dmmt_encode_coefficients(dmmt_ctx* c, const int16_t* coef, size_t
     int rc;
     if ((rc = validate(opt))) return rc;
     Geom g;
-    if ((rc = make_checked_geom(width, height, opt->subsampling, 255, 0, &g))) return rc;
+    if ((rc = make_checked_geom(width, height, opt->subsampling, 255, opt->restart_interval, &g))) return rc;
     if (nblocks != (size_t)g.bpf) return DMMT_E_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = set_device(c))) return rc;

@@ -334,7 +334,7 @@ int dmmt_encode_striped_device(dmmt_ctx* ctx, const dmmt_stripe* stripes, int n,
 int dmmt_forward_blocks(dmmt_ctx* ctx, const dmmt_image* img, const dmmt_options* opt, int16_t* coef,
                         size_t cap_blocks, size_t* nblocks);
 /* Back half only (transformer.rs:199-220 + encoder.rs:125-282): emission-order zigzag
- * blocks (host) -> JPEG file. */
+ * blocks (host) -> JPEG file; opt->restart_interval as in dmmt_jpeg_encode. */
 int dmmt_encode_coefficients(dmmt_ctx* ctx, const int16_t* coef, size_t nblocks, uint16_t width,
                              uint16_t height, const dmmt_options* opt, uint8_t** out, size_t* out_len);
 /* Discrete8x8CosineTransformer::transform_on_threadpool (cosine_transform.rs:55-73) with
