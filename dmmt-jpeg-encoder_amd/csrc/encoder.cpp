@@ -103,6 +103,9 @@ struct dmmt_ctx {
     int ppm_batch_redone = -1;          // files the last batch redid on their own (diagnostic)
     // uploaded table state
     int lut_maxval = -1, lut_sb = -1;
+    // k_front_gray's table of the luma per sample value (gray_fill_lut) and what it was filled for
+    DevBuf gray_lut;
+    int gray_lut_maxval = -1, gray_lut_sb = -1, gray_lut_transfer = -1;
     uint8_t q_cached[128];
     bool q_valid = false;
     // profiling
@@ -188,19 +191,28 @@ void release(DevBuf& b) {
     b.bytes = 0;
 }
 
-int validate(const dmmt_options* opt) {
+// what every call needs of its options; a gray call (one component) needs nothing more:
+// it ignores opt->subsampling and opt->chroma_q
+int validate_gray(const dmmt_options* opt) {
     if (!opt) return DMMT_E_INVALID_ARGUMENT;
-    if (opt->subsampling < 0 || opt->subsampling > 2) return DMMT_E_INVALID_ARGUMENT;
     if (opt->bits_per_channel < 0 || opt->bits_per_channel > 255) return DMMT_E_INVALID_ARGUMENT;
     for (int i = 0; i < 64; ++i)
-        if (opt->luma_q[i] == 0 || opt->chroma_q[i] == 0) return DMMT_E_INVALID_ARGUMENT;
+        if (opt->luma_q[i] == 0) return DMMT_E_INVALID_ARGUMENT;
     if (opt->restart_interval < 0 || opt->restart_interval > 65535) return DMMT_E_INVALID_ARGUMENT;  // DRI is u16
     return DMMT_OK;
 }
 
-int make_checked_geom(int w, int h, int sub, int maxval, int ri, Geom* g) {
+int validate(const dmmt_options* opt) {
+    if (int rc = validate_gray(opt)) return rc;
+    if (opt->subsampling < 0 || opt->subsampling > 2) return DMMT_E_INVALID_ARGUMENT;
+    for (int i = 0; i < 64; ++i)
+        if (opt->chroma_q[i] == 0) return DMMT_E_INVALID_ARGUMENT;
+    return DMMT_OK;
+}
+
+int make_checked_geom(int w, int h, int sub, int maxval, int ri, Geom* g, int ncomp = 3) {
     if (w <= 0 || h <= 0) return DMMT_E_INVALID_ARGUMENT;  // the reference panics on an empty image
-    *g = make_geom(w, h, sub, maxval, ri);
+    *g = make_geom(w, h, sub, maxval, ri, ncomp);
     if (g->wp > 65535 || g->hp > 65535) return DMMT_E_INVALID_ARGUMENT;  // u16 padded size
     return DMMT_OK;
 }
@@ -246,6 +258,26 @@ int upload_tables(dmmt_ctx* c, const dmmt_options* opt, int maxval, int sb, hipS
         c->lut_maxval = maxval;
         c->lut_sb = sb;
     }
+    return DMMT_OK;
+}
+
+// k_front_gray's table for integer samples: the luma of every sample value under
+// (maxval, transfer), filled by front_gray.hip's host side so that it rounds as the
+// device would
+int upload_gray_lut(dmmt_ctx* c, int maxval, int sb, int transfer, hipStream_t st) {
+    if (sb == 4) return DMMT_OK;  // Image<f32> dots: the luma is computed in the kernel
+    if (c->gray_lut_maxval == maxval && c->gray_lut_sb == sb && c->gray_lut_transfer == transfer) return DMMT_OK;
+    int rc;
+    if ((rc = sync_lanes(c))) return rc;  // no lane may still read the old table
+    const size_t n = sb == 1 ? 256 : 65536;
+    if ((rc = ensure(c->gray_lut, n * sizeof(float)))) return rc;
+    std::vector<float> lut(n);
+    gray_fill_lut(lut.data(), n, maxval, transfer);
+    HIP_TRY(hipMemcpyAsync(c->gray_lut.p, lut.data(), n * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    c->gray_lut_maxval = maxval;
+    c->gray_lut_sb = sb;
+    c->gray_lut_transfer = transfer;
     return DMMT_OK;
 }
 
@@ -322,7 +354,9 @@ int prepare(dmmt_ctx* c, const Geom& g, int nf, const dmmt_options* opt, int sb,
     int rc;
     // (allow_narrow: the caller's front end is a k_front kernel and nothing but the
     // entropy kernels reads the blocks after it)
-    const bool narrow = allow_narrow && coef_narrow_for(c->coef_format, sb, opt->luma_q, opt->chroma_q);
+    // (a single-component frame has no chroma blocks: the rule is judged on luma_q alone)
+    const bool narrow = allow_narrow && coef_narrow_for(c->coef_format, sb, opt->luma_q,
+                                                        g.ncomp == 1 ? opt->luma_q : opt->chroma_q);
     if ((rc = ensure_work(c, g, nf, w, lane, async, narrow))) return rc;
     if (status) w->status = status;  // (a per-file status area of dmmt_convert_ppm_device_batch)
     if ((rc = upload_tables(c, opt, g.maxval, sb, st))) return rc;
@@ -414,11 +448,13 @@ int enqueue_back_half(dmmt_ctx* c, const Geom& g, int nf, const Work& w, int bit
 
 int enqueue_direct(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, int nf, const Geom& g,
                    const Work& w, int bits, uint8_t* out, size_t out_stride, uint32_t* out_len, hipStream_t st,
-                   const Surface* sf = nullptr, const YccFrames* yf = nullptr) {
+                   const Surface* sf = nullptr, const YccFrames* yf = nullptr, const GrayPlane* gp = nullptr) {
     {
         StageTimer t(c, ST_FRONT, st);
         const int cap = c->nlanes > 1 ? DMMT_FRONT_PER_CU_LANES : 0;
-        if (yf)  // YCbCr planes (uint8): d_rgb is the luma plane
+        if (gp)  // a one-channel plane: d_rgb is the plane
+            HIP_TRY(launch_front_gray(*gp, frame_stride, sb, nf, g, w, st, cap));
+        else if (yf)  // YCbCr planes (uint8): d_rgb is the luma plane
             HIP_TRY(launch_front_ycc(*yf, frame_stride, nf, g, w, st, cap));
         else if (sf)  // a surface: d_rgb is its first plane
             HIP_TRY(launch_front_surface(*sf, frame_stride, sb, nf, g, w, st, cap));
@@ -440,15 +476,23 @@ void destroy_graphs(dmmt_ctx* c) {
 int enqueue_encode(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, int nf, const Geom& g,
                    const dmmt_options* opt, uint8_t* out, size_t out_stride, uint32_t* out_len, hipStream_t st,
                    int lane = 0, bool async = false, int* status = nullptr, const Surface* sf = nullptr,
-                   const YccFrames* yf = nullptr) {
+                   const YccFrames* yf = nullptr, const GrayPlane* gray = nullptr) {
     Work w;
     int rc;
     if ((rc = prepare(c, g, nf, opt, sb, st, &w, lane, async, status, true))) return rc;
+    GrayPlane gpv{};
+    const GrayPlane* gp = nullptr;
+    if (gray) {  // the caller's description, with the table bound here
+        if ((rc = upload_gray_lut(c, g.maxval, sb, gray->transfer, st))) return rc;
+        gpv = *gray;
+        gpv.lut = sb == 4 ? nullptr : (const float*)c->gray_lut.p;
+        gp = &gpv;
+    }
     const int bits = opt->bits_per_channel;
     // (a per-file status area -- dmmt_convert_ppm_device_batch -- would put a new
     // pointer into every file's graph key: that path launches directly)
     if (!c->use_graphs || c->profile || status)
-        return enqueue_direct(c, d_rgb, frame_stride, sb, nf, g, w, bits, out, out_stride, out_len, st, sf, yf);
+        return enqueue_direct(c, d_rgb, frame_stride, sb, nf, g, w, bits, out, out_stride, out_len, st, sf, yf, gp);
     std::vector<uint64_t> key = {(uint64_t)(uintptr_t)d_rgb, (uint64_t)frame_stride, (uint64_t)sb, (uint64_t)nf,
                                  (uint64_t)g.width, (uint64_t)g.height, (uint64_t)g.hr, (uint64_t)g.vr,
                                  (uint64_t)g.maxval, (uint64_t)g.restart_interval, (uint64_t)bits,
@@ -461,6 +505,13 @@ int enqueue_encode(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, 
     if (yf)  // YCbCr planes: two descriptions may share their luma pointer
         key.insert(key.end(), {(uint64_t)yf->format + 16, (uint64_t)yf->luma_pitch, (uint64_t)yf->chroma_pitch,
                                (uint64_t)(uintptr_t)yf->plane[1], (uint64_t)(uintptr_t)yf->plane[2]});
+    // a gray call and a 4:4:4 colour call of the same size share every field above: the
+    // component count, the transfer (through the table's contents the graph reads, and the
+    // table's address), the plane and its pitch
+    key.push_back((uint64_t)g.ncomp);
+    if (gp)
+        key.insert(key.end(), {(uint64_t)gp->transfer + 32, (uint64_t)(uintptr_t)gp->lut,
+                               (uint64_t)(uintptr_t)gp->plane, (uint64_t)gp->row_pitch});
     const void* const* wp = reinterpret_cast<const void* const*>(&w);
     static_assert(sizeof(Work) % sizeof(void*) == 0, "Work holds pointers only");
     for (size_t i = 0; i < sizeof(Work) / sizeof(void*); ++i) key.push_back((uint64_t)(uintptr_t)wp[i]);
@@ -470,7 +521,7 @@ int enqueue_encode(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, 
     if (!hit) {
         hipGraph_t graph = nullptr;
         HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        rc = enqueue_direct(c, d_rgb, frame_stride, sb, nf, g, w, bits, out, out_stride, out_len, st, sf, yf);
+        rc = enqueue_direct(c, d_rgb, frame_stride, sb, nf, g, w, bits, out, out_stride, out_len, st, sf, yf, gp);
         hipError_t e = hipStreamEndCapture(st, &graph);
         if (rc) {
             if (graph) (void)hipGraphDestroy(graph);
@@ -619,7 +670,7 @@ int ctx_check_device(dmmt_ctx* c) {
         for (const DevBuf* b : bufs)
             if ((rc = check_ptr_device(b->p, c->device))) return rc;
     }
-    const DevBuf* bufs[] = {&c->lut, &c->qtab, &c->qtab_u8, &c->in, &c->out, &c->out_len, &c->dct, &c->ppm_text,
+    const DevBuf* bufs[] = {&c->lut, &c->gray_lut, &c->qtab, &c->qtab_u8, &c->in, &c->out, &c->out_len, &c->dct, &c->ppm_text,
                             &c->ppm_maps, &c->ppm_chunk_in, &c->ppm_misc, &c->ppm_counts};
     for (const DevBuf* b : bufs)
         if ((rc = check_ptr_device(b->p, c->device))) return rc;
@@ -675,7 +726,7 @@ extern "C" void dmmt_ctx_destroy(dmmt_ctx* c) {
     for (size_t i = 0; i < c->lanes.size(); ++i) destroy_lane(c->lanes[i], i > 0);
     if (c->ev_lane0) (void)hipEventDestroy(c->ev_lane0);
     if (c->ev_caller) (void)hipEventDestroy(c->ev_caller);
-    DevBuf* bufs[] = {&c->lut,      &c->qtab,         &c->qtab_u8,  &c->in,       &c->out,     &c->out_len,
+    DevBuf* bufs[] = {&c->lut,      &c->gray_lut, &c->qtab,         &c->qtab_u8,  &c->in,       &c->out,     &c->out_len,
                       &c->dct,      &c->ppm_text,     &c->ppm_maps, &c->ppm_chunk_in, &c->ppm_misc,
                       &c->ppm_counts};
     for (DevBuf* b : bufs) release(*b);
@@ -735,7 +786,8 @@ extern "C" size_t dmmt_max_jpeg_bytes(uint16_t width, uint16_t height, int32_t s
 // plane is f->d_rgb) and dmmt_encode_device_ycc (yf: the planes, f->d_rgb the luma
 // plane) after their own argument checks
 static int encode_device_frames(dmmt_ctx* c, const dmmt_device_frames* f, const dmmt_options* opt, void* stream,
-                                const Geom& g, const Surface* sf, const YccFrames* yf = nullptr) {
+                                const Geom& g, const Surface* sf, const YccFrames* yf = nullptr,
+                                const GrayPlane* gp = nullptr) {
     int rc;
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = set_device(c))) return rc;
@@ -746,7 +798,7 @@ static int encode_device_frames(dmmt_ctx* c, const dmmt_device_frames* f, const 
         HIP_TRY(hipEventRecord(c->ev_lane0, c->stream));
         HIP_TRY(hipStreamWaitEvent(st, c->ev_lane0, 0));
         rc = enqueue_encode(c, f->d_rgb, f->frame_stride, f->sample_bytes, f->n_frames, g, opt, f->d_out,
-                            f->out_stride, f->d_out_len, st, 0, true, nullptr, sf, yf);
+                            f->out_stride, f->d_out_len, st, 0, true, nullptr, sf, yf, gp);
         HIP_TRY(hipEventRecord(c->ev_caller, st));
         HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_caller, 0));
         return rc;
@@ -754,7 +806,7 @@ static int encode_device_frames(dmmt_ctx* c, const dmmt_device_frames* f, const 
     int lane = 0;  // pipelined: the next lane's workspace and stream
     if (c->nlanes > 1) lane = (int)(c->next_lane++ % (unsigned)c->nlanes);
     return enqueue_encode(c, f->d_rgb, f->frame_stride, f->sample_bytes, f->n_frames, g, opt, f->d_out, f->out_stride,
-                          f->d_out_len, c->lanes[lane]->stream, lane, true, nullptr, sf, yf);
+                          f->d_out_len, c->lanes[lane]->stream, lane, true, nullptr, sf, yf, gp);
 }
 
 extern "C" int dmmt_encode_device(dmmt_ctx* c, const dmmt_device_frames* f, const dmmt_options* opt, void* stream) {
@@ -852,6 +904,105 @@ extern "C" int dmmt_encode_device_ycc(dmmt_ctx* c, const dmmt_device_ycc* y, con
     f.width = y->width, f.height = y->height, f.maxval = 255, f.sample_bytes = 1;
     f.d_out = y->d_out, f.out_stride = y->out_stride, f.d_out_len = y->d_out_len;
     return encode_device_frames(c, &f, opt, stream, g, nullptr, &yf);
+}
+
+// the checks dmmt_encode_device_gray and dmmt_jpeg_encode_gray share
+static int check_gray(int transfer, int sample_bytes, int maxval) {
+    if (transfer != DMMT_GRAY_AS_RGB && transfer != DMMT_GRAY_Y_FULL_RANGE) return DMMT_E_INVALID_ARGUMENT;
+    if (sample_bytes != 1 && sample_bytes != 2 && sample_bytes != 4) return DMMT_E_INVALID_ARGUMENT;
+    if (transfer == DMMT_GRAY_Y_FULL_RANGE && sample_bytes != 1) return DMMT_E_INVALID_ARGUMENT;
+    // integer samples are normalised by v / maxval: the table has no meaning for maxval 0
+    if (transfer == DMMT_GRAY_AS_RGB && sample_bytes != 4 && maxval == 0) return DMMT_E_INVALID_ARGUMENT;
+    return DMMT_OK;
+}
+// (Y_FULL_RANGE: uint8 samples cannot exceed 255, whatever maxval says)
+static int gray_maxval(int transfer, int maxval) { return transfer == DMMT_GRAY_Y_FULL_RANGE ? 255 : maxval; }
+
+extern "C" size_t dmmt_gray_span(const dmmt_device_gray* s) {
+    if (!s) return 0;
+    return gray_plane_span(s->width, s->height, s->sample_bytes, s->row_pitch);
+}
+
+extern "C" size_t dmmt_max_gray_jpeg_bytes(uint16_t width, uint16_t height) {
+    if (width == 0 || height == 0) return 0;
+    return max_jpeg_bytes(make_geom(width, height, 0, 255, 0, 1));
+}
+
+extern "C" int dmmt_encode_device_gray(dmmt_ctx* c, const dmmt_device_gray* s, const dmmt_options* opt, void* stream) {
+    c = primary(c);
+    if (!c || !s) return DMMT_E_INVALID_ARGUMENT;
+    int rc;
+    if ((rc = validate_gray(opt))) return rc;
+    if (s->n_frames <= 0 || !s->d_out || !s->d_out_len) return DMMT_E_INVALID_ARGUMENT;
+    if ((rc = check_gray(s->transfer, s->sample_bytes, s->maxval))) return rc;
+    const size_t sb = s->sample_bytes;
+    if (!s->d_plane || (uintptr_t)s->d_plane % sb) return DMMT_E_INVALID_ARGUMENT;
+    if (s->row_pitch < (size_t)s->width * sb || s->row_pitch % sb || s->row_pitch > DMMT_MAX_ROW_PITCH ||
+        s->frame_stride % sb)
+        return DMMT_E_INVALID_ARGUMENT;
+    Geom g;
+    if ((rc = make_checked_geom(s->width, s->height, 0, gray_maxval(s->transfer, s->maxval), opt->restart_interval, &g, 1)))
+        return rc;
+    if (s->out_stride < max_jpeg_bytes(g)) return DMMT_E_CAPACITY;
+    GrayPlane gp{};
+    gp.plane = s->d_plane;
+    gp.row_pitch = s->row_pitch;
+    gp.transfer = s->transfer;
+    dmmt_device_frames f{};
+    f.d_rgb = s->d_plane;
+    f.frame_stride = s->frame_stride;
+    f.n_frames = s->n_frames;
+    f.width = s->width, f.height = s->height, f.maxval = (uint16_t)g.maxval, f.sample_bytes = s->sample_bytes;
+    f.d_out = s->d_out, f.out_stride = s->out_stride, f.d_out_len = s->d_out_len;
+    return encode_device_frames(c, &f, opt, stream, g, nullptr, nullptr, &gp);
+}
+
+// A host image of one sample per pixel -> a host JPEG (dmmt_jpeg_encode's steps).
+extern "C" int dmmt_jpeg_encode_gray(dmmt_ctx* c, const dmmt_gray_image* img, const dmmt_options* opt, uint8_t** out,
+                                     size_t* out_len) {
+    c = primary(c);
+    if (!c || !out || !out_len) return DMMT_E_INVALID_ARGUMENT;
+    *out = nullptr;
+    *out_len = 0;
+    int rc;
+    if ((rc = validate_gray(opt))) return rc;
+    if (!img || !img->gray || img->width == 0 || img->height == 0) return DMMT_E_INVALID_ARGUMENT;
+    if ((rc = check_gray(img->transfer, img->sample_bytes, img->maxval))) return rc;
+    Geom g;
+    if ((rc = make_checked_geom(img->width, img->height, 0, gray_maxval(img->transfer, img->maxval),
+                                opt->restart_interval, &g, 1)))
+        return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    const size_t pitch = (size_t)img->width * img->sample_bytes;
+    const size_t frame_bytes = pitch * img->height;
+    const size_t out_stride = (max_jpeg_bytes(g) + 255) / 256 * 256;
+    if ((rc = ensure(c->in, frame_bytes))) return rc;
+    if ((rc = ensure(c->out, out_stride))) return rc;
+    if ((rc = ensure(c->out_len, sizeof(uint32_t)))) return rc;
+    hipStream_t st = c->stream;
+    HIP_TRY(hipMemcpyAsync(c->in.p, img->gray, frame_bytes, hipMemcpyHostToDevice, st));
+    GrayPlane gp{};
+    gp.plane = c->in.p;
+    gp.row_pitch = pitch;
+    gp.transfer = img->transfer;
+    if ((rc = enqueue_encode(c, c->in.p, 0, img->sample_bytes, 1, g, opt, (uint8_t*)c->out.p, out_stride,
+                             (uint32_t*)c->out_len.p, st, 0, false, nullptr, nullptr, nullptr, &gp)))
+        return rc;
+    uint32_t L = 0;
+    HIP_TRY(hipMemcpyAsync(&L, c->out_len.p, sizeof L, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = take_status(c, st))) return rc;
+    if (L == 0 || L > out_stride) return DMMT_E_CAPACITY;
+    uint8_t* h = (uint8_t*)malloc(L);
+    if (!h) return DMMT_E_OUT_OF_MEMORY;
+    if (hipMemcpy(h, c->out.p, L, hipMemcpyDeviceToHost) != hipSuccess) {
+        free(h);
+        return DMMT_E_HIP;
+    }
+    *out = h;
+    *out_len = L;
+    return DMMT_OK;
 }
 
 // Host-memory batch of equal-geometry images -> host JPEGs.

@@ -60,18 +60,22 @@ struct Geom {
     int bit_phase;          // global scan bit offset of the stripe's first bit, mod 8
     int next_bits;          // bits of the scan after the stripe known here (0..16)
     uint32_t next16;        // those bits, MSB-aligned in 16
+    int ncomp;              // components of the file: 3 (Y, Cb, Cr), or 1 (a grayscale frame: luma only)
 };
 
-inline Geom make_geom(int width, int height, int subsampling, int maxval, int restart_interval) {
+// ncomp 1: a single-component (grayscale) frame -- sampling 1x1, an MCU is one
+// block and the blocks lie in raster order; `subsampling` is ignored
+inline Geom make_geom(int width, int height, int subsampling, int maxval, int restart_interval, int ncomp = 3) {
     Geom g{};
     g.width = width;
     g.height = height;
-    g.hr = subsampling == 0 ? 1 : 2;
-    g.vr = subsampling == 2 ? 2 : 1;
+    g.ncomp = ncomp == 1 ? 1 : 3;
+    g.hr = subsampling == 0 || g.ncomp == 1 ? 1 : 2;
+    g.vr = subsampling == 2 && g.ncomp != 1 ? 2 : 1;
     g.wp = (width + 8 * g.hr - 1) / (8 * g.hr) * (8 * g.hr);
     g.hp = (height + 8 * g.vr - 1) / (8 * g.vr) * (8 * g.vr);
     g.n_luma = g.hr * g.vr;
-    g.bpm = g.n_luma + 2;
+    g.bpm = g.n_luma + (g.ncomp == 1 ? 0 : 2);
     g.mcux = g.wp / (8 * g.hr);
     g.mcuy = g.hp / (8 * g.vr);
     g.nmcu = g.mcux * g.mcuy;

@@ -886,6 +886,69 @@ __device__ __forceinline__ void put_be16(uint8_t* p, int v) {
     p[1] = (uint8_t)v;
 }
 
+// write_table_header for a single-component (grayscale) file, g.ncomp == 1: the
+// colour header with every chroma part taken out and the order kept -- SOI, APP0,
+// one DQT (Tq 0), SOF0 of length 11 (Nf 1, component 01 11 00), DHT luma AC, DHT
+// luma DC, [DRI], the 10-byte SOS.  Only tables 0 and 1 are built (nt[2] = nt[3] = 0).
+__device__ void write_table_header_gray(uint8_t* o, int tab, int t0, int step, int n, const int nt[4],
+                                        const uint8_t* symrank, const int* bits16, const Geom& g,
+                                        const uint8_t* __restrict__ qtab_u8, int bits_per_channel,
+                                        uint32_t* hdr_len, int dq) {
+    if (tab > 1) return;
+    const int off_lac = 2 + 18 + 69 + 13;
+    const int off_ldc = off_lac + 21 + nt[1];
+    const int dht = tab == 0 ? off_ldc : off_lac;
+    for (int s = t0; s < n; s += step) o[dht + 21 + s] = symrank[n - 1 - s];
+    for (int s = t0; s < 16; s += step) o[dht + 5 + s] = (uint8_t)bits16[s];
+    if (t0 == 0) {
+        uint8_t* d = o + dht;
+        d[0] = 0xFF;
+        d[1] = 0xC4;
+        put_be16(d + 2, 2 + 17 + n);
+        d[4] = tab == 0 ? 0x00 : 0x11;
+    }
+    if (tab != 0) return;
+    const int pos_after_dht = off_ldc + 21 + nt[0];
+    const int pos_sos = pos_after_dht + (g.restart_interval > 0 ? 6 : 0);
+    if (t0 == 0) {
+        o[0] = 0xFF;
+        o[1] = 0xD8;  // SOI
+        const uint8_t app0[18] = {0xFF, 0xE0, 0x00, 0x10, 'J', 'F', 'I', 'F', 0, 0x01, 0x02, 0x00, 0x00, 0x48, 0x00, 0x48, 0, 0};
+        for (int i = 0; i < 18; ++i) o[2 + i] = app0[i];
+        uint8_t* d = o + 20;  // DQT, the luma table in zigzag order
+        d[0] = 0xFF;
+        d[1] = 0xDB;
+        put_be16(d + 2, 67);
+        d[4] = 0;
+        uint8_t* sof = o + 89;
+        sof[0] = 0xFF;
+        sof[1] = 0xC0;
+        put_be16(sof + 2, 11);
+        sof[4] = (uint8_t)bits_per_channel;
+        put_be16(sof + 5, g.sof_height);
+        put_be16(sof + 7, g.width);
+        sof[9] = 1;
+        sof[10] = 1;
+        sof[11] = 0x11;
+        sof[12] = 0;
+        if (g.restart_interval > 0) {  // extension: DRI
+            uint8_t* r = o + pos_after_dht;
+            r[0] = 0xFF;
+            r[1] = 0xDD;
+            put_be16(r + 2, 4);
+            put_be16(r + 4, g.restart_interval);
+        }
+        const uint8_t sos[10] = {0xFF, 0xDA, 0x00, 0x08, 0x01, 0x01, 0x01, 0x00, 0x3F, 0x00};
+        for (int i = 0; i < 10; ++i) o[pos_sos + i] = sos[i];
+        *hdr_len = (uint32_t)(pos_sos + 10);
+    }
+    if (dq >= 0) {
+        o[25 + t0] = (uint8_t)dq;
+        return;
+    }
+    for (int s = t0; s < 64; s += step) o[25 + s] = qtab_u8[c_zigzag[s]];
+}
+
 // The table's DHT segment (encoder.rs:169-181: BITS, then the symbols most frequent
 // first, i.e. symrank -- symbols by ascending frequency -- reversed) and, for table
 // 0, SOI, APP0, DQT x2, SOF0, [DRI], SOS (encoder.rs:125-262) and the header length;
@@ -899,6 +962,10 @@ __device__ void write_table_header(uint8_t* o, int tab, int t0, int step, int n,
                                    int dq = -1) {
     if (!g.stripe_first) {  // a later stripe of an image: tables only, no header
         if (tab == 0 && t0 == 0) *hdr_len = 0;
+        return;
+    }
+    if (g.ncomp == 1) {  // (uniform) a single-component file
+        write_table_header_gray(o, tab, t0, step, n, nt, symrank, bits16, g, qtab_u8, bits_per_channel, hdr_len, dq);
         return;
     }
     const int pos_dht0 = 2 + 18 + 69 + 69 + 19;
@@ -1402,138 +1469,144 @@ __device__ __forceinline__ void tables_tail(uint8_t* lds, const uint32_t* ac_his
     unsigned long long* const Key = reinterpret_cast<unsigned long long*>(F + cap);
     uint8_t* const Sym = reinterpret_cast<uint8_t*>(F + 3 * cap);
     int* const bits16 = sBits + 16 * tab;
+    // a single-component frame has no chroma tables: waves 2 and 3 build nothing,
+    // report nothing and leave their code-table rows alone
+    const bool idle = g.ncomp == 1 && tab >= 2;  // (wave-uniform)
+    int n = 0, dq = -1;
+    if (idle) {
+        if (lane == 0) sCnt[tab] = 0;
+    } else {
+        // ---- 1 (AC: symbols lane + 64 q; DC: symbol lane < 16 -- coalesced loads)
+        uint32_t f[4] = {0u, 0u, 0u, 0u};
+        if (ac) {
+            const uint32_t* h = ac_hist + ((size_t)frame * kHistReps * 2 + c) * 256 + lane;
+#pragma unroll
+            for (int r = 0; r < kHistReps; ++r)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) f[q] += ld_agent(h + (size_t)r * 512 + 64 * q);
+        } else if (lane < 16) {
+            const uint32_t* h = dc_hist + (size_t)frame * kHistReps * 32 + c * 16 + lane;
+#pragma unroll
+            for (int r = 0; r < kHistReps; ++r) f[0] += ld_agent(h + (size_t)r * 32);
+        }
+        // table 0's wave: its lane's DQT bytes (zigzag position lane of both tables, kept
+        // in zigzag order by the host), loaded with the histograms rather than after
+        // the tables
+        if (tab == 0 && g.stripe_first) dq = (int)qtab_u8[128 + lane] | ((int)qtab_u8[192 + lane] << 8);
+        // keys (frequency << 8 | symbol): u32 while every frequency is below 2^24
+        const bool k32 = __ballot(((f[0] | f[1] | f[2] | f[3]) >> 24) != 0u) == 0ull;
+        uint32_t* const ct = code_tab + ((size_t)frame * 4 + tab) * 256;
+        unsigned long long pres[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            pres[q] = __ballot(f[q] > 0u);
+            if (f[q] == 0u) ct[lane + 64 * q] = 0;  // (a present symbol's entry: phase 5)
+            n += __popcll(pres[q]);
+        }
+        // k_tables' checks: a table without symbols; symbol 0xFF in an AC table (the
+        // reference's lookup table has 255 entries)
+        raise_status(status, ((lane == 0 && n == 0) || (ac && lane == 63 && f[3] > 0u)) ? 2 : 0);  // (s 255: lane 63, q 3)
+        if (lane == 0) sCnt[tab] = n;  // (read by every wave in phase 6, after the barrier)
+        if (lane < 16) bits16[lane] = 0;
 
-    // ---- 1 (AC: symbols lane + 64 q; DC: symbol lane < 16 -- coalesced loads)
-    uint32_t f[4] = {0u, 0u, 0u, 0u};
-    if (ac) {
-        const uint32_t* h = ac_hist + ((size_t)frame * kHistReps * 2 + c) * 256 + lane;
+        // ---- 2: the present keys in ascending order (absent symbols: kMergeInf, last)
+        // -> F (frequency), Sym by leaf rank
+        if (k32) {
+            if (ac && (!DMMT_TAIL_SORT2 || n > 128)) {
+                uint32_t x[4];
 #pragma unroll
-        for (int r = 0; r < kHistReps; ++r)
+                for (int q = 0; q < 4; ++q) x[q] = f[q] ? (f[q] << 8) | (uint32_t)(lane + 64 * q) : kMergeInf;
+                sort_bitonic<4>(x);
 #pragma unroll
-            for (int q = 0; q < 4; ++q) f[q] += ld_agent(h + (size_t)r * 512 + 64 * q);
-    } else if (lane < 16) {
-        const uint32_t* h = dc_hist + (size_t)frame * kHistReps * 32 + c * 16 + lane;
+                for (int q = 0; q < 4; ++q)
+                    if (lane + 64 * q < n) {
+                        F[lane + 64 * q] = x[q] >> 8;
+                        Sym[lane + 64 * q] = (uint8_t)x[q];
+                    }
+            } else if (ac) {  // (uniform) at most 128 present symbols: compacted into two slots, half the network
+                uint32_t* const K32 = reinterpret_cast<uint32_t*>(Key);
+                int at = 0;
 #pragma unroll
-        for (int r = 0; r < kHistReps; ++r) f[0] += ld_agent(h + (size_t)r * 32);
-    }
-    // table 0's wave: its lane's DQT bytes (zigzag position lane of both tables, kept
-    // in zigzag order by the host), loaded with the histograms rather than after
-    // the tables
-    int dq = -1;
-    if (tab == 0 && g.stripe_first) dq = (int)qtab_u8[128 + lane] | ((int)qtab_u8[192 + lane] << 8);
-    // keys (frequency << 8 | symbol): u32 while every frequency is below 2^24
-    const bool k32 = __ballot(((f[0] | f[1] | f[2] | f[3]) >> 24) != 0u) == 0ull;
-    uint32_t* const ct = code_tab + ((size_t)frame * 4 + tab) * 256;
-    int n = 0;
-    unsigned long long pres[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        pres[q] = __ballot(f[q] > 0u);
-        if (f[q] == 0u) ct[lane + 64 * q] = 0;  // (a present symbol's entry: phase 5)
-        n += __popcll(pres[q]);
-    }
-    // k_tables' checks: a table without symbols; symbol 0xFF in an AC table (the
-    // reference's lookup table has 255 entries)
-    raise_status(status, ((lane == 0 && n == 0) || (ac && lane == 63 && f[3] > 0u)) ? 2 : 0);  // (s 255: lane 63, q 3)
-    if (lane == 0) sCnt[tab] = n;  // (read by every wave in phase 6, after the barrier)
-    if (lane < 16) bits16[lane] = 0;
-
-    // ---- 2: the present keys in ascending order (absent symbols: kMergeInf, last)
-    // -> F (frequency), Sym by leaf rank
-    if (k32) {
-        if (ac && (!DMMT_TAIL_SORT2 || n > 128)) {
-            uint32_t x[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) x[q] = f[q] ? (f[q] << 8) | (uint32_t)(lane + 64 * q) : kMergeInf;
-            sort_bitonic<4>(x);
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (lane + 64 * q < n) {
-                    F[lane + 64 * q] = x[q] >> 8;
-                    Sym[lane + 64 * q] = (uint8_t)x[q];
+                for (int q = 0; q < 4; ++q) {
+                    if (f[q]) K32[at + __popcll(pres[q] & ((1ull << lane) - 1ull))] = (f[q] << 8) | (uint32_t)(lane + 64 * q);
+                    at += __popcll(pres[q]);
                 }
-        } else if (ac) {  // (uniform) at most 128 present symbols: compacted into two slots, half the network
-            uint32_t* const K32 = reinterpret_cast<uint32_t*>(Key);
+                wave_lds_sync();
+                uint32_t x[2] = {lane < n ? K32[lane] : kMergeInf, lane + 64 < n ? K32[lane + 64] : kMergeInf};
+                sort_bitonic<2>(x);
+#pragma unroll
+                for (int q = 0; q < 2; ++q)
+                    if (lane + 64 * q < n) {
+                        F[lane + 64 * q] = x[q] >> 8;
+                        Sym[lane + 64 * q] = (uint8_t)x[q];
+                    }
+            } else {
+                uint32_t x[1] = {f[0] ? (f[0] << 8) | (uint32_t)lane : kMergeInf};
+                sort_bitonic<1>(x);
+                if (lane < n) {
+                    F[lane] = x[0] >> 8;
+                    Sym[lane] = (uint8_t)x[0];
+                }
+            }
+        } else {  // rank among 64-bit keys, compacted slot by slot (order immaterial: the keys carry their symbols)
             int at = 0;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                if (f[q]) K32[at + __popcll(pres[q] & ((1ull << lane) - 1ull))] = (f[q] << 8) | (uint32_t)(lane + 64 * q);
+                if (f[q]) Key[at + __popcll(pres[q] & ((1ull << lane) - 1ull))] = ((unsigned long long)f[q] << 8) | (unsigned)(lane + 64 * q);
                 at += __popcll(pres[q]);
             }
             wave_lds_sync();
-            uint32_t x[2] = {lane < n ? K32[lane] : kMergeInf, lane + 64 < n ? K32[lane + 64] : kMergeInf};
-            sort_bitonic<2>(x);
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-                if (lane + 64 * q < n) {
-                    F[lane + 64 * q] = x[q] >> 8;
-                    Sym[lane + 64 * q] = (uint8_t)x[q];
-                }
-        } else {
-            uint32_t x[1] = {f[0] ? (f[0] << 8) | (uint32_t)lane : kMergeInf};
-            sort_bitonic<1>(x);
-            if (lane < n) {
-                F[lane] = x[0] >> 8;
-                Sym[lane] = (uint8_t)x[0];
-            }
-        }
-    } else {  // rank among 64-bit keys, compacted slot by slot (order immaterial: the keys carry their symbols)
-        int at = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (f[q]) Key[at + __popcll(pres[q] & ((1ull << lane) - 1ull))] = ((unsigned long long)f[q] << 8) | (unsigned)(lane + 64 * q);
-            at += __popcll(pres[q]);
+            tail_rank_any(Key, n, F, Sym);
         }
         wave_lds_sync();
-        tail_rank_any(Key, n, F, Sym);
-    }
-    wave_lds_sync();
 
-    // ---- 3, 4 (wave-uniform choice of the merge width)
-    int leaf[kTailLevels];
-    if (n <= 32)
-        tail_levels<1>(F, n, leaf);
-    else if (n <= 64)
-        tail_levels<2>(F, n, leaf);
-    else if (n <= 128)
-        tail_levels<4>(F, n, leaf);
-    else
-        tail_levels<8>(F, n, leaf);
+        // ---- 3, 4 (wave-uniform choice of the merge width)
+        int leaf[kTailLevels];
+        if (n <= 32)
+            tail_levels<1>(F, n, leaf);
+        else if (n <= 64)
+            tail_levels<2>(F, n, leaf);
+        else if (n <= 128)
+            tail_levels<4>(F, n, leaf);
+        else
+            tail_levels<8>(F, n, leaf);
 
-    uint32_t len[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int i = lane + 64 * r;
-        len[r] = 0;
-        if (i < n) {
-            uint32_t L = i == 0 ? 1u : 0u;
-#pragma unroll
-            for (int k = 0; k < kTailLevels; ++k) L += i < leaf[k] ? 1u : 0u;
-            len[r] = L;
-            atomicAdd(&bits16[L - 1], 1);
-        }
-    }
-
-    // ---- 5: code(rank i) = sum over the ranks above i of 2^(16 - len), mod 2^16
-    {
-        uint32_t carry = 0;
-        uint32_t inc[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const uint32_t wgt = len[r] ? 1u << (16 - len[r]) : 0u;
-            inc[r] = carry + wave_incl_scan_full_u32(wgt);
-            carry = (uint32_t)__builtin_amdgcn_readlane((int)inc[r], 63);
-        }
+        uint32_t len[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int i = lane + 64 * r;
+            len[r] = 0;
             if (i < n) {
-                const uint32_t pat = (carry - inc[r]) & 0xFFFFu;  // left aligned u16 (wrapping as in the reference)
-                ct[Sym[i]] = (len[r] << 16) | (pat >> (16 - len[r]));
+                uint32_t L = i == 0 ? 1u : 0u;
+#pragma unroll
+                for (int k = 0; k < kTailLevels; ++k) L += i < leaf[k] ? 1u : 0u;
+                len[r] = L;
+                atomicAdd(&bits16[L - 1], 1);
+            }
+        }
+
+        // ---- 5: code(rank i) = sum over the ranks above i of 2^(16 - len), mod 2^16
+        {
+            uint32_t carry = 0;
+            uint32_t inc[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const uint32_t wgt = len[r] ? 1u << (16 - len[r]) : 0u;
+                inc[r] = carry + wave_incl_scan_full_u32(wgt);
+                carry = (uint32_t)__builtin_amdgcn_readlane((int)inc[r], 63);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int i = lane + 64 * r;
+                if (i < n) {
+                    const uint32_t pat = (carry - inc[r]) & 0xFFFFu;  // left aligned u16 (wrapping as in the reference)
+                    ct[Sym[i]] = (len[r] << 16) | (pat >> (16 - len[r]));
+                }
             }
         }
     }
     __syncthreads();  // every table's count (sCnt); this wave's BITS
+    if (idle) return;
 
     // ---- 6
     const int nt[4] = {sCnt[0], sCnt[1], sCnt[2], sCnt[3]};
@@ -1785,7 +1858,9 @@ hipError_t launch_hist(int n_frames, const Geom& g, const Work& w, int check_cat
 
 hipError_t launch_tables(int n_frames, const Geom& g, const Work& w, int bits_per_channel, uint8_t* out,
                          size_t out_stride, hipStream_t st) {
-    hipLaunchKernelGGL(k_tables, dim3(4, n_frames), dim3(512), 0, st, (const uint32_t*)w.ac_hist,
+    // (a single-component frame: the luma tables only; the chroma histograms are
+    // empty, so every workgroup counts nt[2] = nt[3] = 0)
+    hipLaunchKernelGGL(k_tables, dim3(g.ncomp == 1 ? 2 : 4, n_frames), dim3(512), 0, st, (const uint32_t*)w.ac_hist,
                        (const uint32_t*)w.dc_hist, w.code_tab, out, out_stride,
                        w.hdr_len, g, w.qtab_u8, bits_per_channel, w.status);
     return hipGetLastError();

@@ -72,6 +72,23 @@ size_t ycc_plane_span(int format, int plane, int width, int height, int hr, int 
 hipError_t launch_front_ycc(const YccFrames& yf, size_t frame_stride_bytes, int n_frames, const Geom& g, const Work& w,
                             hipStream_t st, int per_cu_cap = 0);
 
+// A one-channel plane (dmmt_device_gray): transfer as dmmt_gray_transfer
+enum { GRAY_AS_RGB = 0, GRAY_Y_FULL_RANGE = 1 };
+struct GrayPlane {
+    const void* plane;
+    size_t row_pitch;  // bytes between rows
+    int transfer;      // GRAY_AS_RGB or GRAY_Y_FULL_RANGE: what the table holds
+    const float* lut;  // device: the luma per sample value (gray_fill_lut); unused for float samples
+};
+// bytes from the plane's first byte to one past its last, per frame; 0: a bad description
+size_t gray_plane_span(int width, int height, int sample_bytes, size_t row_pitch);
+// the luma of sample values 0 .. n-1 as k_front_gray's table holds them (host)
+void gray_fill_lut(float* lut, size_t n, int maxval, int transfer);
+// k_front_gray (front_gray.hip): the plane -> w.coef, as launch_front; g from
+// make_geom(..., ncomp = 1)
+hipError_t launch_front_gray(const GrayPlane& gp, size_t frame_stride_bytes, int sample_bytes, int n_frames,
+                             const Geom& g, const Work& w, hipStream_t st, int per_cu_cap = 0);
+
 // per_cu_cap: at most this many resident k_front workgroups per CU (0: as many as
 // fit, 4); a context of several lanes passes DMMT_FRONT_PER_CU_LANES
 hipError_t launch_front(const void* rgb, size_t frame_stride_bytes, int sample_bytes, int n_frames, const Geom& g,

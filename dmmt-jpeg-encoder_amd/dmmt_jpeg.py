@@ -91,6 +91,12 @@ def lib():
     L.dmmt_encode_device_ycc.argtypes = [vp, P(DmmtDeviceYcc), P(DmmtOptions), vp]
     L.dmmt_ycc_plane_span.argtypes = [P(DmmtDeviceYcc), ctypes.c_int]
     L.dmmt_ycc_plane_span.restype = sz
+    L.dmmt_encode_device_gray.argtypes = [vp, P(DmmtDeviceGray), P(DmmtOptions), vp]
+    L.dmmt_gray_span.argtypes = [P(DmmtDeviceGray)]
+    L.dmmt_gray_span.restype = sz
+    L.dmmt_max_gray_jpeg_bytes.argtypes = [u16, u16]
+    L.dmmt_max_gray_jpeg_bytes.restype = sz
+    L.dmmt_jpeg_encode_gray.argtypes = [vp, P(DmmtGrayImage), P(DmmtOptions), P(vp), P(sz)]
     L.dmmt_ctx_set_lanes.argtypes = [vp, ctypes.c_int]
     L.dmmt_max_jpeg_bytes.argtypes = [u16, u16, i32]
     L.dmmt_max_jpeg_bytes.restype = sz
@@ -217,6 +223,35 @@ class YccFormat(enum.IntEnum):
 def ycc_plane_span(y: DmmtDeviceYcc, plane: int) -> int:
     """dmmt_ycc_plane_span: the bytes of a plane the encoder may read, per frame"""
     return int(lib().dmmt_ycc_plane_span(ctypes.byref(y), int(plane)))
+
+
+class DmmtDeviceGray(ctypes.Structure):
+    _fields_ = [("d_plane", ctypes.c_void_p), ("row_pitch", ctypes.c_size_t), ("frame_stride", ctypes.c_size_t),
+                ("n_frames", ctypes.c_int32), ("transfer", ctypes.c_int32),
+                ("width", ctypes.c_uint16), ("height", ctypes.c_uint16), ("maxval", ctypes.c_uint16),
+                ("sample_bytes", ctypes.c_uint16), ("d_out", ctypes.c_void_p), ("out_stride", ctypes.c_size_t),
+                ("d_out_len", ctypes.c_void_p)]
+
+
+class DmmtGrayImage(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_uint16), ("height", ctypes.c_uint16), ("maxval", ctypes.c_uint16),
+                ("sample_bytes", ctypes.c_uint16), ("gray", ctypes.c_void_p), ("transfer", ctypes.c_int32)]
+
+
+class GrayTransfer(enum.IntEnum):
+    """dmmt_gray_transfer: how a one-channel sample becomes the DCT's input"""
+    AS_RGB = 0        # the luma of the pixel (v, v, v) through the reference's path
+    Y_FULL_RANGE = 1  # uint8 JFIF luma: s - 128, dmmt_encode_device_ycc's Y
+
+
+def gray_span(g: DmmtDeviceGray) -> int:
+    """dmmt_gray_span: the bytes of the plane the encoder may read, per frame"""
+    return int(lib().dmmt_gray_span(ctypes.byref(g)))
+
+
+def max_gray_jpeg_bytes(width: int, height: int) -> int:
+    """dmmt_max_gray_jpeg_bytes: the worst-case size of a single-component file"""
+    return int(lib().dmmt_max_gray_jpeg_bytes(width, height))
 
 
 class DmmtStripe(ctypes.Structure):
@@ -651,6 +686,101 @@ class Encoder:
             for ptr in ptrs:
                 self.free(ptr)
 
+    @staticmethod
+    def gray(d_plane: int, row_pitch: int, n_frames: int, width: int, height: int, d_out: int = 0,
+             out_stride: int = 0, d_out_len: int = 0, frame_stride: int = 0, maxval: int = 255,
+             sample_bytes: int = 1, transfer: int = GrayTransfer.AS_RGB) -> DmmtDeviceGray:
+        """fill a dmmt_device_gray struct (nothing is enqueued)"""
+        g = DmmtDeviceGray()
+        g.d_plane, g.row_pitch, g.frame_stride = d_plane, row_pitch, frame_stride
+        g.n_frames, g.transfer = n_frames, int(transfer)
+        g.width, g.height, g.maxval, g.sample_bytes = width, height, maxval, sample_bytes
+        g.d_out, g.out_stride, g.d_out_len = d_out, out_stride, d_out_len
+        return g
+
+    def encode_device_gray(self, d_plane: int, row_pitch: int, n_frames: int, width: int, height: int,
+                           options: JpegTransformationOptions, d_out: int, out_stride: int, d_out_len: int,
+                           frame_stride: int = 0, maxval: int = 255, sample_bytes: int = 1,
+                           transfer: int = GrayTransfer.AS_RGB, stream: int | None = None,
+                           opt_c: DmmtOptions | None = None):
+        """dmmt_encode_device_gray: a one-channel plane in HBM -> single-component JPEG
+        files; options' subsampling and chroma table are ignored; enqueued, see
+        synchronize()"""
+        opt = opt_c if opt_c is not None else options.to_c()
+        g = self.gray(d_plane, row_pitch, n_frames, width, height, d_out, out_stride, d_out_len, frame_stride, maxval,
+                      sample_bytes, transfer)
+        _check(lib().dmmt_encode_device_gray(self._ctx, ctypes.byref(g), ctypes.byref(opt), stream),
+               "encode_device_gray")
+
+    def encode_gray(self, array, maxval: int = 255, options: JpegTransformationOptions = None,
+                    transfer: int = GrayTransfer.AS_RGB) -> bytes:
+        """One frame from a host array (H, W) of uint8, uint16 (with maxval) or float32
+        (normalised dots): uploaded, encoded as a single-component file and freed."""
+        if options is None:
+            options = JpegTransformationOptions()
+        a = np.asarray(array)
+        sizes = {np.dtype(np.uint8): 1, np.dtype(np.uint16): 2, np.dtype(np.float32): 4}
+        if a.dtype not in sizes:
+            raise ValueError(f"dtype {a.dtype}: uint8, uint16 or float32 samples are supported")
+        if a.ndim != 2 or 0 in a.shape:
+            raise ValueError("shape (H, W) is required")
+        h, w = a.shape
+        if w > 65535 or h > 65535:
+            raise ValueError("at most 65535 x 65535 pixels")
+        a = np.ascontiguousarray(a)
+        sb = sizes[a.dtype]
+        cap = max_gray_jpeg_bytes(w, h)
+        ptrs = []
+        try:
+            d_in = self.malloc(a.nbytes)
+            ptrs.append(d_in)
+            self.h2d(d_in, a)
+            d_out = self.malloc(cap)
+            ptrs.append(d_out)
+            d_len = self.malloc(4)
+            ptrs.append(d_len)
+            self.encode_device_gray(d_in, w * sb, 1, w, h, options, d_out, cap, d_len, maxval=int(maxval),
+                                    sample_bytes=sb, transfer=transfer)
+            self.synchronize()
+            n = int(np.frombuffer(self.d2h(d_len, 4), np.uint32)[0])
+            return self.d2h(d_out, min(n, cap))
+        finally:
+            for ptr in ptrs:
+                self.free(ptr)
+
+    def _tensor_gray(self, t, maxval):
+        """(plane, row_pitch, frame_stride, n_frames, width, height, maxval, sample_bytes)
+        of a one-channel tensor (H, W), or (N, H, W), on this encoder's GPU"""
+        if torch is None:
+            raise RuntimeError("encode_tensor needs torch")
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError("a torch tensor in device memory is required")
+        if t.device.index != self.device:
+            raise ValueError(f"the tensor is on {t.device}, the encoder on GPU {self.device}")
+        sizes = {torch.uint8: 1, torch.int16: 2, torch.float32: 4}
+        if hasattr(torch, "uint16"):
+            sizes[torch.uint16] = 2
+        if t.dtype not in sizes:
+            raise ValueError(f"dtype {t.dtype}: uint8, int16/uint16 or float32 samples are supported")
+        sb = sizes[t.dtype]
+        if t.dim() not in (2, 3):
+            raise ValueError("HW: shape (H,W), with an optional batch dimension, is required")
+        if 0 in t.shape:
+            raise ValueError("an empty tensor")
+        (h, w), (s_h, s_w) = t.shape[-2:], t.stride()[-2:]
+        if w > 1 and s_w != 1:
+            raise ValueError("HW: the samples of a row must be contiguous (stride 1 along W)")
+        pitch = s_h * sb if h > 1 else w * sb
+        if pitch < w * sb:
+            raise ValueError("rows overlap (a row stride below the row's samples)")
+        n = t.shape[0] if t.dim() == 3 else 1
+        fstride = t.stride()[0] * sb if t.dim() == 3 and n > 1 else 0
+        if w > 65535 or h > 65535:
+            raise ValueError("at most 65535 x 65535 pixels")
+        if maxval is None:
+            maxval = 255 if sb == 1 else 65535
+        return t.data_ptr(), pitch, fstride, n, w, h, int(maxval), sb
+
     def _tensor_surface(self, t, layout, maxval):
         """(planes, format, row_pitch, frame_stride, n_frames, width, height, maxval,
         sample_bytes) of a tensor on this encoder's GPU, from its pointer and strides"""
@@ -715,7 +845,7 @@ class Encoder:
         return planes, fmt, pitch, fstride, n, w, h, int(maxval), sb
 
     def encode_tensor_device(self, t, options: JpegTransformationOptions, *, layout: str | None = None,
-                             maxval: int | None = None):
+                             maxval: int | None = None, transfer: int | None = None):
         """Encode a tensor where it lies: uint8, int16/uint16 or (normalised) float32,
         shape (H,W,3), (H,W,4) or (3,H,W) with an optional batch dimension, any row,
         plane and batch strides (a crop or slice of a larger tensor is fine), samples
@@ -724,9 +854,21 @@ class Encoder:
         does not fit raises ValueError.  Ordered on torch's current stream, nothing is
         synchronised; returns (out, lens): uint8 [n, out_stride] and int32 [n] device
         tensors, JPEG f = out[f, :lens[f]].  Errors the kernels find are raised by
-        synchronize()."""
-        planes, fmt, pitch, fstride, n, w, h, mv, sb = self._tensor_surface(t, layout, maxval)
-        cap = max_jpeg_bytes(w, h, int(options.chroma_subsampling_preset))
+        synchronize().
+        layout "HW" (never guessed): a one-channel tensor (H,W), or (N,H,W), or a strided
+        view of one, encoded in place as single-component files (transfer: GrayTransfer,
+        which no other layout takes: ValueError)."""
+        gray = (layout or "").upper() == "HW"
+        if not gray and transfer is not None:
+            raise ValueError("transfer= applies to layout=\"HW\" only")
+        if transfer is None:
+            transfer = GrayTransfer.AS_RGB
+        if gray:
+            plane, pitch, fstride, n, w, h, mv, sb = self._tensor_gray(t, maxval)
+            cap = max_gray_jpeg_bytes(w, h)
+        else:
+            planes, fmt, pitch, fstride, n, w, h, mv, sb = self._tensor_surface(t, layout, maxval)
+            cap = max_jpeg_bytes(w, h, int(options.chroma_subsampling_preset))
         out = torch.empty((n, cap), dtype=torch.uint8, device=t.device)
         lens = torch.empty((n,), dtype=torch.int32, device=t.device)
         cur = torch.cuda.current_stream(t.device)
@@ -739,9 +881,14 @@ class Encoder:
                 self._tensor_stream = torch.cuda.Stream(t.device)
             run = self._tensor_stream
             run.wait_stream(cur)
-        self.encode_device_surfaces(planes if fmt == PixelFormat.PLANAR else planes[0], fmt, pitch, n, w, h, options,
-                                    out.data_ptr(), cap, lens.data_ptr(), frame_stride=fstride, maxval=mv,
-                                    sample_bytes=sb, stream=run.cuda_stream)
+        if gray:
+            self.encode_device_gray(plane, pitch, n, w, h, options, out.data_ptr(), cap, lens.data_ptr(),
+                                    frame_stride=fstride, maxval=mv, sample_bytes=sb, transfer=transfer,
+                                    stream=run.cuda_stream)
+        else:
+            self.encode_device_surfaces(planes if fmt == PixelFormat.PLANAR else planes[0], fmt, pitch, n, w, h,
+                                        options, out.data_ptr(), cap, lens.data_ptr(), frame_stride=fstride,
+                                        maxval=mv, sample_bytes=sb, stream=run.cuda_stream)
         if run is not cur:
             # t, out and lens belong to cur's allocator pool but are used on run: that
             # is safe only because cur waits for run here, before it can reuse them
@@ -749,10 +896,10 @@ class Encoder:
         return out, lens
 
     def encode_tensor(self, t, options: JpegTransformationOptions, *, layout: str | None = None,
-                      maxval: int | None = None):
+                      maxval: int | None = None, transfer: int | None = None):
         """encode_tensor_device, one synchronize and a copy back: a list of bytes, one
         JPEG per frame"""
-        out, lens = self.encode_tensor_device(t, options, layout=layout, maxval=maxval)
+        out, lens = self.encode_tensor_device(t, options, layout=layout, maxval=maxval, transfer=transfer)
         self.synchronize()
         n = lens.cpu().tolist()
         host = out.cpu().numpy()

@@ -238,6 +238,71 @@ int dmmt_encode_device_ycc(dmmt_ctx* ctx, const dmmt_device_ycc* ycc, const dmmt
  * description or a plane the format does not use */
 size_t dmmt_ycc_plane_span(const dmmt_device_ycc* ycc, int plane);
 
+/* ---- grayscale frames (extension) -----------------------------------------------------------
+ * One-channel frames -- a mono camera, an IR or depth sensor, a scanned page, the Y plane of a
+ * decoder's NV12 -- written as single-component JPEG files.  The reference has no gray input
+ * (Image<f32> is always RGB), so the contract is stated in its stages:
+ *  - one component, sampling 1x1: an MCU is one 8x8 block, the blocks in raster order; width and
+ *    height are padded to multiples of 8 (padder.rs with hr = vr = 1).  opt->subsampling and
+ *    opt->chroma_q are ignored; opt->luma_q, bits_per_channel and restart_interval (in MCUs,
+ *    here blocks) mean what they mean elsewhere;
+ *  - DMMT_GRAY_AS_RGB: the sample v is the pixel (v, v, v) taken through the reference's path --
+ *    integer samples normalised by color.rs:45-53 (sample_bytes 4: Image<f32> dots as they
+ *    are), luma by color.rs:75-100, (((n*0.299f + n*0.587f) + n*0.114f) - 128f/255f) * 255f in
+ *    that order; padding is the black pixel, that expression at n = 0.  sample_bytes 1, 2 (with
+ *    maxval, which must not be 0) and 4; a sample above maxval is DMMT_E_VALUE_EXCEEDS_MAX.  The file's coefficients
+ *    are the luma coefficients of the reference's 4:4:4 file of the replicated image;
+ *  - DMMT_GRAY_Y_FULL_RANGE (uint8 only, maxval ignored): a sample s enters the DCT as
+ *    (float)s - 128 and padding is sample 0 -- the luma contract of dmmt_encode_device_ycc, so
+ *    the Y plane of an NV12 or I420 frame is encoded by pointing at it;
+ *  - from there the reference's path: the Arai DCT, round(d/q) with the luma table, zigzag, DC
+ *    differences along the single chain of blocks (reset at restart boundaries), package-merge
+ *    tables from the luma DC and AC histograms only, bit packing, 1-padding, 0xFF00
+ *    stuffing, RSTn, EOI;
+ *  - the header is the colour header with every chroma part taken out and the order kept: SOI,
+ *    the 18 APP0 bytes, one DQT (Tq 0), SOF0 of length 11 (Nf 1, component 01 11 00), DHT luma
+ *    AC (0x11), DHT luma DC (0x00), DRI when restart_interval > 0, SOS FF DA 00 08 01 01 01
+ *    00 3F 00.
+ * Pitch rules, the region of interest and the read guarantee are those of
+ * dmmt_device_surfaces: for frame f only bytes of [d_plane + f * frame_stride, ... +
+ * dmmt_gray_span(g)) are read, and only the rectangle's samples influence the output. */
+enum dmmt_gray_transfer {
+    DMMT_GRAY_AS_RGB = 0,        /* the luma of the pixel (v, v, v) */
+    DMMT_GRAY_Y_FULL_RANGE = 1   /* uint8 JFIF luma: s - 128 */
+};
+typedef struct dmmt_device_gray {
+    const void* d_plane;     /* the rectangle's first sample, a multiple of sample_bytes */
+    size_t row_pitch;        /* bytes between rows; >= width * sample_bytes, a multiple of sample_bytes,
+                                <= DMMT_MAX_ROW_PITCH */
+    size_t frame_stride;     /* bytes between frames, a multiple of sample_bytes */
+    int32_t n_frames;
+    int32_t transfer;        /* dmmt_gray_transfer */
+    uint16_t width, height, maxval, sample_bytes;  /* as dmmt_image, one sample per pixel */
+    uint8_t* d_out; size_t out_stride; uint32_t* d_out_len;   /* as dmmt_device_frames; out_stride >=
+                                                                 dmmt_max_gray_jpeg_bytes(width, height) */
+} dmmt_device_gray;
+/* Stream, lanes and errors as dmmt_encode_device_surfaces (NULL stream: round-robin over the
+ * lanes; a caller's stream is tied to lane 0 in both directions; errors through
+ * dmmt_ctx_synchronize; a multi-GPU context: member 0). */
+int dmmt_encode_device_gray(dmmt_ctx* ctx, const dmmt_device_gray* gray, const dmmt_options* opt, void* stream);
+/* bytes from the plane's first byte to one past its last: (height-1)*row_pitch +
+ * width*sample_bytes; 0 for an unsupported description */
+size_t dmmt_gray_span(const dmmt_device_gray* gray);
+/* worst-case size of a gray file; never larger than dmmt_max_jpeg_bytes(w, h, DMMT_P444) */
+size_t dmmt_max_gray_jpeg_bytes(uint16_t width, uint16_t height);
+/* A host image of one sample per pixel (dmmt_image with `gray` for `rgb`, plus the transfer):
+ * uploaded, encoded and returned as dmmt_jpeg_encode returns a colour file. */
+typedef struct dmmt_gray_image {
+    uint16_t width;
+    uint16_t height;
+    uint16_t maxval;
+    uint16_t sample_bytes;
+    const void* gray;        /* row-major, tightly packed */
+    int32_t transfer;        /* dmmt_gray_transfer */
+} dmmt_gray_image;
+int dmmt_jpeg_encode_gray(dmmt_ctx* ctx, const dmmt_gray_image* img, const dmmt_options* opt, uint8_t** out,
+                          size_t* out_len);
+
 /* ---- one image across several GPUs (extension) ---------------------------------------- */
 /* A run of whole MCU rows of one image (BASELINE config 4): with a restart
  * interval (dmmt_options.restart_interval > 0) every stripe that starts and ends on an
