@@ -350,8 +350,14 @@ int ensure_work(dmmt_ctx* c, const Geom& g, int nf, Work* w, int lane, bool asyn
 
 // workspace + tables for one launch batch; every table pointer is valid on return
 int prepare(dmmt_ctx* c, const Geom& g, int nf, const dmmt_options* opt, int sb, hipStream_t st, Work* w,
-            int lane = 0, bool async = false, int* status = nullptr, bool allow_narrow = false) {
+            int lane = 0, bool async = false, int* status = nullptr, bool allow_narrow = false,
+            bool stripe_step = false) {
     int rc;
+    // A pending stripe's blocks and measured chunks lie in lane 0's workspace, and its
+    // tables in the shared ones: any other call that gets this far, on any lane, may
+    // overwrite or reallocate either, so it invalidates the stripe (the later stripe
+    // step then returns DMMT_E_INVALID_ARGUMENT before it launches anything)
+    if (!stripe_step) c->stripe_pending = c->stripe_measured = false;
     // (allow_narrow: the caller's front end is a k_front kernel and nothing but the
     // entropy kernels reads the blocks after it)
     // (a single-component frame has no chroma blocks: the rule is judged on luma_q alone)
@@ -1720,7 +1726,8 @@ extern "C" int dmmt_stripe_analyze(dmmt_ctx* c, const dmmt_stripe* st, const dmm
     if ((rc = set_device(c))) return rc;
     hipStream_t s = c->stream;
     Work w;
-    if ((rc = prepare(c, g, 1, opt, st->sample_bytes, s, &w, 0, false, nullptr, true))) return rc;
+    c->stripe_pending = c->stripe_measured = false;  // replaced by this stripe, or by none if this call fails
+    if ((rc = prepare(c, g, 1, opt, st->sample_bytes, s, &w, 0, false, nullptr, true, true))) return rc;
     {
         StageTimer t(c, ST_FRONT, s);
         HIP_TRY(launch_front(st->d_rgb, (size_t)st->width * g.height * 3 * st->sample_bytes, st->sample_bytes, 1, g, w,
@@ -1842,7 +1849,7 @@ extern "C" int dmmt_stripe_measure(dmmt_ctx* c, const uint64_t hist_sum[DMMT_STR
     if (out_cap < max_jpeg_bytes(g)) return DMMT_E_CAPACITY;
     hipStream_t s = c->stream;
     Work w;
-    if ((rc = prepare(c, g, 1, &c->stripe_opt, c->stripe_sb, s, &w, 0, false, nullptr, true))) return rc;
+    if ((rc = prepare(c, g, 1, &c->stripe_opt, c->stripe_sb, s, &w, 0, false, nullptr, true, true))) return rc;
     if ((rc = upload_hist_sum(w, hist_sum, s))) return rc;
     // the stripe's first DC differences continue the previous stripe's predictors
     int16_t d[3];
@@ -1898,7 +1905,7 @@ extern "C" int dmmt_stripe_write(dmmt_ctx* c, uint64_t bit_offset, uint32_t next
     g.next16 = g.more_after ? (next16 & 0xFFFFu) & ~(0xFFFFu >> next_bits) : 0u;
     hipStream_t s = c->stream;
     Work w;
-    if ((rc = prepare(c, g, 1, &c->stripe_opt, c->stripe_sb, s, &w, 0, false, nullptr, true))) return rc;
+    if ((rc = prepare(c, g, 1, &c->stripe_opt, c->stripe_sb, s, &w, 0, false, nullptr, true, true))) return rc;
     if ((rc = ensure(c->out_len, 4))) return rc;
     {
         StageTimer t(c, ST_OFFSETS, s);
@@ -1931,7 +1938,7 @@ extern "C" int dmmt_stripe_encode(dmmt_ctx* c, const uint64_t hist_sum[DMMT_STRI
     if (out_cap < max_jpeg_bytes(g)) return DMMT_E_CAPACITY;
     hipStream_t s = c->stream;
     Work w;
-    if ((rc = prepare(c, g, 1, &c->stripe_opt, c->stripe_sb, s, &w, 0, false, nullptr, true))) return rc;
+    if ((rc = prepare(c, g, 1, &c->stripe_opt, c->stripe_sb, s, &w, 0, false, nullptr, true, true))) return rc;
     // the summed histograms go into replica 0 (the other replicas are zero)
     if ((rc = upload_hist_sum(w, hist_sum, s))) return rc;
     if ((rc = ensure(c->out_len, 4))) return rc;

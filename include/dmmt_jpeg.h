@@ -315,7 +315,14 @@ int dmmt_jpeg_encode_gray(dmmt_ctx* ctx, const dmmt_gray_image* img, const dmmt_
  *                        follow) or EOI (the image ends)
  * The stripes' outputs concatenated in row order are byte-identical to dmmt_jpeg_encode of
  * the whole image with the same restart interval.  Without restart intervals see
- * "joined stripes" below. */
+ * "joined stripes" below.
+ * The analysed stripe lives in the context's workspace between the steps.  Any other call on
+ * the context that encodes or transforms (dmmt_jpeg_encode*, dmmt_encode_device* on any lane
+ * or stream, dmmt_forward_blocks, dmmt_encode_coefficients, the PPM conversions) invalidates
+ * it: dmmt_stripe_encode, _dc_edges, _measure and _write then return
+ * DMMT_E_INVALID_ARGUMENT until a new dmmt_stripe_analyze, which also replaces a pending
+ * stripe.  Device memory calls, copies, dmmt_fill_synthetic*, dmmt_ctx_synchronize,
+ * _set_lanes, _set_profiling, _profile and _check_device leave the stripe intact. */
 typedef struct dmmt_stripe {
     const void* d_rgb;          /* device: the stripe's pixel rows only, interleaved R,G,B */
     uint16_t width, height;     /* the whole image */
