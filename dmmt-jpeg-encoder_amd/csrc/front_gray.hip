@@ -26,6 +26,7 @@
 
 #include "dct_quant.hpp"
 #include "device_common.hpp"
+#include "front_common.hpp"
 #include "front_launch.hpp"
 #include "gray_load.hpp"
 #include "jpeg_common.hpp"
@@ -51,46 +52,24 @@ struct GrayArgs {
     const uint8_t* p;
     GrayDesc d;
 };
-struct GrayMem {
-    const uint8_t* base;
-    __device__ __forceinline__ void load16(long long off, uint32_t (&w)[4]) const {
-        const uint4 v = ld16_nt(base + off);
-        w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
-    }
-    __device__ __forceinline__ uint32_t load1(long long off) const { return base[off]; }
-    __device__ __forceinline__ uint32_t base_lo() const { return (uint32_t)(uintptr_t)base; }
-};
-
-// N words from byte offset `off` (any alignment) of the 16-byte aligned LDS array
-// s: the N + 1 aligned words that hold them, funnel-shifted (v_alignbyte_b32).
-// Reads at most 3 bytes past the N words.  (front_ycc.hip's)
-template <int N>
-__device__ __forceinline__ void gray_lds_words(const uint8_t* s, int off, uint32_t (&o)[N]) {
-    const uint32_t* a = reinterpret_cast<const uint32_t*>(s + (off & ~3));
-    uint32_t t[N + 1];
-#pragma unroll
-    for (int i = 0; i <= N; ++i) t[i] = a[i];
-#pragma unroll
-    for (int i = 0; i < N; ++i) o[i] = __builtin_amdgcn_alignbyte(t[i + 1], t[i], (uint32_t)off & 3u);
-}
 
 // One workgroup (256 threads) per tile = 32 horizontally adjacent blocks of one
 // block row (256 columns, 8 rows), a grid-stride loop over the frame's tiles
 // (blockIdx.y = frame) with the next tile's bytes prefetched into registers while
-// this one computes -- k_front's shape (kernels.hip, front_body), with the same
-// skewed block-major LDS layout of the row-transformed blocks (sT, blk_base).
+// this one computes -- k_front's shape, from the same pieces (front_common.hpp):
+// the one-component FrontGeom with k_front's skewed block-major LDS layout of the
+// row-transformed blocks (sT, blk_base), front_stage and front_column_pass.
 //  staging  GrayTile / gray_tile_chunk (gray_load.hpp): 8 tile rows, each at its own
 //     misalignment; past the rectangle everything stages as 0
 //  A  one thread per (row r, block c): its 8 samples from LDS -- the table's luma
 //     per integer sample (u8: the table in LDS), gray_luma of a float dot -- and the
 //     row pass.  Integer samples: the largest one against maxval where a sample can
 //     exceed it (color.rs:63-65, status bit 1)
-//  C, D  as k_front: one lane per (block, column) -- column pass, quantise
-//     (integer samples quantize_col8_scaled, whose bound holds as for k_front: the
-//     luma of a sample in range lies in [-128, 128], and no NaN can arise -- the host
-//     refuses maxval 0 for integer samples -- so nan_possible = false; float dots are
-//     unbounded and may be NaN: arai8 and quantize_col8, wide blocks only), one
-//     16-byte store per lane at el = the block's raster index.
+//  C, D  front_column_pass (integer samples quantize_col8_scaled, whose bound holds
+//     as for k_front: the luma of a sample in range lies in [-128, 128], and no NaN
+//     can arise -- the host refuses maxval 0 for integer samples -- so nan_possible =
+//     false; float dots are unbounded and may be NaN: arai8 and quantize_col8, wide
+//     blocks only), the blocks at el = their raster index.
 // NARROW: the 80-byte block form (coef_format.hpp), as front_body's.
 template <typename Sample, bool NARROW>
 __device__ __forceinline__ void front_gray_body(const GrayArgs& ga, size_t frame_stride, const Geom& g,
@@ -101,27 +80,20 @@ __device__ __forceinline__ void front_gray_body(const GrayArgs& ga, size_t frame
     constexpr int SB = (int)sizeof(Sample);
     static_assert(!NARROW || SB != 4, "Image<f32> dots are unbounded: wide blocks");
     using T = GrayTile<SB>;
-    constexpr int NB = 32;  // blocks per tile
-    constexpr int BS = 72;  // LDS floats per block (front_body)
-    auto blk_base = [](int b) { return b * BS + 4 * ((b >> 2) & 1); };  // (front_body's luma blocks)
+    using G = FrontGeom<1, 1, 1>;  // 32 blocks per tile, an MCU is one block (front_common.hpp)
 
-    __shared__ __attribute__((aligned(16))) float sT[NB * BS + 4];
-    __shared__ __attribute__((aligned(16))) uint8_t sRaw[T::BYTES + 16];  // (+ 16: gray_lds_words reads 3 bytes past a row)
+    __shared__ __attribute__((aligned(16))) float sT[G::ST_FLOATS];
+    __shared__ __attribute__((aligned(16))) uint8_t sRaw[T::BYTES + 16];  // (+ 16: lds_words reads 3 bytes past a row)
     __shared__ float sLut[SB == 1 ? 256 : 1];
     __shared__ float sQ[64];
-    __shared__ float sRQ[64];  // 1/q, correctly rounded; integer samples: fl(scale_row * fl(1/q))
+    __shared__ float sRQ[64];
 
     const int tid = threadIdx.x;
     const int frame = blockIdx.y;
-    const GrayMem m{ga.p + (size_t)frame * frame_stride};
+    const PlaneMem m{ga.p + (size_t)frame * frame_stride};
     const GrayDesc& d = ga.d;
-    if (tid < 64) sQ[tid] = qtab[tid];
-    if (tid < 64) sRQ[tid] = SB == 4 ? 1.0f / qtab[tid] : c_arai_scale[(tid >> 3) & 7] * (1.0f / qtab[tid]);
+    front_fill_qtabs<G, SB != 4>(qtab, sQ, sRQ, tid);
     if constexpr (SB == 1) sLut[tid] = lut[tid];
-    const int col = tid & 7;  // the column pass handles column tid & 7 of block tid >> 3
-
-    const int tiles_per_row = (g.mcux + NB - 1) / NB;
-    const int ntiles = tiles_per_row * g.mcuy;
     int bad = 0;
     const bool check_range = SB != 4 && g.maxval < (SB == 1 ? 255 : 65535);
 
@@ -136,30 +108,25 @@ __device__ __forceinline__ void front_gray_body(const GrayArgs& ga, size_t frame
             raw[i] = make_uint4(w[0], w[1], w[2], w[3]);
         }
     };
+    const int tiles_per_row = (g.mcux + G::TM - 1) / G::TM;
+    const int ntiles = tiles_per_row * g.mcuy;
     if ((int)blockIdx.x < ntiles) {
         const int my = blockIdx.x / tiles_per_row;
-        load_tile((blockIdx.x - my * tiles_per_row) * 256, my * 8);
+        load_tile((blockIdx.x - my * tiles_per_row) * 256, my * G::ROWS);
     }
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int my = tile / tiles_per_row;
-        const int mx0 = (tile - my * tiles_per_row) * NB;
-        const int x0 = mx0 * 8;
-        const int y0 = my * 8;
-
-#pragma unroll
-        for (int i = 0; i < T::NQ; ++i) {
-            const int q = tid + 256 * i;
-            if (q < T::NCHUNK) reinterpret_cast<uint4*>(sRaw)[q] = raw[i];
-        }
+        const int mx0 = (tile - my * tiles_per_row) * G::TM;
+        const int x0 = mx0 * 8 * G::HR, y0 = my * G::ROWS;
+        front_stage<T::NCHUNK>(sRaw, tid, raw);
         __syncthreads();
         {  // prefetch the next tile's bytes; they land while this tile computes
             const int nt = tile + gridDim.x;
             if (nt < ntiles) {
                 const int ny = nt / tiles_per_row;
-                load_tile((nt - ny * tiles_per_row) * 256, ny * 8);
+                load_tile((nt - ny * tiles_per_row) * 256, ny * G::ROWS);
             }
         }
-
         // ---- A: sample -> luma (color.rs:45-53, 75-100), row pass (arai.rs:97-99)
         {
             const int c = tid & 31, r = tid >> 5;  // block, row
@@ -172,7 +139,7 @@ __device__ __forceinline__ void front_gray_body(const GrayArgs& ga, size_t frame
                 for (int k = 0; k < 8; ++k) v[k] = gray_luma(src[k]);
             } else {
                 uint32_t w[2 * SB];
-                gray_lds_words<2 * SB>(sRaw, off, w);
+                lds_words<2 * SB>(sRaw, off, w);
                 uint32_t smax = 0;  // largest sample of the row (a sample above maxval panics in color.rs:63-65)
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
@@ -183,43 +150,12 @@ __device__ __forceinline__ void front_gray_body(const GrayArgs& ga, size_t frame
                 if (check_range) bad |= (int)(smax > (uint32_t)g.maxval);  // status bit 1
             }
             arai8(v);
-            float4* o = reinterpret_cast<float4*>(sT + blk_base(c) + r * 8);
+            float4* o = reinterpret_cast<float4*>(sT + G::blk_base(c) + r * 8);
             o[0] = make_float4(v[0], v[1], v[2], v[3]);
             o[1] = make_float4(v[4], v[5], v[6], v[7]);
         }
         __syncthreads();
-
-        // ---- C: column pass (stride 8, arai.rs:100-102), quantise (quantizer.rs:53-62)
-        // ---- D: the tile's blocks in raster order, only those inside the image
-        const int nvalid = min(NB, g.mcux - mx0);
-        const long long e0 = (long long)frame * g.bpf + ((long long)my * g.mcux + mx0);
-        int16_t* const cbase = coef + e0 * 64;  // (uniform: the stores take a 32-bit lane offset)
-        {
-            const int el = tid >> 3;
-            int x[8];
-            {
-                float v[8];
-                const float* tb = sT + blk_base(el) + col;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) v[i] = tb[i * 8];
-                if constexpr (SB == 4) {  // Image<f32> dots: unbounded coefficients
-                    arai8(v);
-                    quantize_col8(v, sQ + col, sRQ + col, x);
-                } else {
-                    arai8_unscaled(v);
-                    quantize_col8_scaled(v, sQ + col, sRQ + col, false, x);
-                }
-            }
-            const bool valid = el < nvalid;  // (uniform over the block's 8 lanes)
-            if constexpr (NARROW) {
-                coef_store_column_narrow(x, col, el, valid, cbase, coef_lo + e0 * 8, coef_hi + e0 * 64);
-            } else if (valid) {
-                uint32_t pk[4];  // the low halves of two coefficients per word (one v_perm_b32)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) pk[i] = __builtin_amdgcn_perm((uint32_t)x[2 * i + 1], (uint32_t)x[2 * i], 0x05040100u);
-                *reinterpret_cast<uint4*>(cbase + (el * 64 + 8 * col)) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-            }
-        }
+        front_column_pass<G, NARROW, SB == 4>(sT, sQ, sRQ, tid, false, g, frame, mx0, my, coef, coef_lo, coef_hi);
     }
     if (bad) raise_status(status, bad);  // 1: sample above maxval
 }
@@ -252,18 +188,13 @@ constexpr int front_gray_wpe() {
 template <typename S>
 static void front_gray_impl(const GrayArgs& ga, size_t frame_stride, int n_frames, const Geom& g, const Work& w,
                             const float* lut, hipStream_t st, int per_cu_cap) {
-    const long long ntiles = (long long)((g.mcux + 31) / 32) * g.mcuy;
-    if constexpr (sizeof(S) != 4) {
-        if (w.coef_lo) {
-            static const FrontCfg cfgn = [] { return front_cfg(k_front_gray_n<S, front_gray_wpe<S>()>); }();
-            hipLaunchKernelGGL((k_front_gray_n<S, front_gray_wpe<S>()>), front_grid(cfgn, ntiles, n_frames, per_cu_cap),
-                               dim3(256), 0, st, ga, frame_stride, g, lut, w.qtab, w.coef, w.status, w.coef_lo, w.coef_hi);
-            return;
-        }
-    }
-    static const FrontCfg cfg = [] { return front_cfg(k_front_gray<S, front_gray_wpe<S>()>); }();
-    hipLaunchKernelGGL((k_front_gray<S, front_gray_wpe<S>()>), front_grid(cfg, ntiles, n_frames, per_cu_cap), dim3(256), 0,
-                       st, ga, frame_stride, g, lut, w.qtab, w.coef, w.status);
+    constexpr int WPE = front_gray_wpe<S>();
+    if constexpr (sizeof(S) == 4)  // (float samples have no narrow twin)
+        front_launch<k_front_gray<S, WPE>, nullptr>(g, n_frames, per_cu_cap, st, w.coef_lo, w.coef_hi, ga, frame_stride,
+                                                    g, lut, w.qtab, w.coef, w.status);
+    else
+        front_launch<k_front_gray<S, WPE>, k_front_gray_n<S, WPE>>(g, n_frames, per_cu_cap, st, w.coef_lo, w.coef_hi, ga,
+                                                                   frame_stride, g, lut, w.qtab, w.coef, w.status);
 }
 
 size_t gray_plane_span(int width, int height, int sample_bytes, size_t row_pitch) {

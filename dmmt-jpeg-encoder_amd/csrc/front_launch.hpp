@@ -1,18 +1,21 @@
-// front_launch.hpp -- the grid of a front kernel (kernels.hip: k_front,
-// k_front_surf; front_ycc.hip: k_front_ycc): host code shared by their launchers.
+// front_launch.hpp -- the grid and the launch of a front kernel (kernels.hip:
+// k_front, k_front_surf; front_ycc.hip: k_front_ycc; front_gray.hip: k_front_gray;
+// each with a narrow twin, *_n): host code shared by their launchers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
+
+#include "jpeg_common.hpp"
 
 namespace dmmt {
 
 static inline int clampi(long long v, int lo, int hi) { return (int)(v < lo ? lo : (v > hi ? hi : v)); }
 
 // The resident workgroups of one front-kernel instantiation: one workgroup per
-// resident slot, each looping over tiles and prefetching the next.  A launcher
-// keeps one as a function static, computed once (thread-safe initialisation).
+// resident slot, each looping over tiles and prefetching the next.
 struct FrontCfg {
     int resident, n_cus;
     bool per_cu_env;
@@ -35,6 +38,41 @@ static FrontCfg front_cfg(K kernel) {
 static inline dim3 front_grid(const FrontCfg& cfg, long long ntiles, int n_frames, int per_cu_cap) {
     const int res = per_cu_cap > 0 && !cfg.per_cu_env ? std::min(cfg.resident, per_cu_cap * cfg.n_cus) : cfg.resident;
     return dim3(clampi(ntiles, 1, res / n_frames > 0 ? res / n_frames : 1), n_frames);
+}
+
+// One launch of the instantiation Wide, or of its narrow twin Narrow (nullptr: it
+// has none) when the call stores narrow blocks (coef_lo set): the twin takes the
+// wide kernel's arguments, then coef_lo and coef_hi.  A tile is 32 / g.hr MCUs.
+// Each kernel's FrontCfg is a function static, computed once (thread-safe
+// initialisation).
+template <auto Kernel, typename... Args>
+static void front_launch_one(const Geom& g, int n_frames, int per_cu_cap, hipStream_t st, Args... args) {
+    static const FrontCfg cfg = front_cfg(Kernel);
+    const int tm = 32 / g.hr;
+    const long long ntiles = (long long)((g.mcux + tm - 1) / tm) * g.mcuy;
+    hipLaunchKernelGGL(Kernel, front_grid(cfg, ntiles, n_frames, per_cu_cap), dim3(256), 0, st, args...);
+}
+template <auto Wide, auto Narrow, typename... Args>
+static void front_launch(const Geom& g, int n_frames, int per_cu_cap, hipStream_t st, int16_t* coef_lo, int8_t* coef_hi,
+                         Args... args) {
+    if constexpr (!std::is_null_pointer_v<decltype(Narrow)>) {
+        if (coef_lo) return front_launch_one<Narrow>(g, n_frames, per_cu_cap, st, args..., coef_lo, coef_hi);
+    }
+    front_launch_one<Wide>(g, n_frames, per_cu_cap, st, args...);
+}
+
+// f(HR, VR) with the chroma sampling of g as two std::integral_constants: 4:4:4
+// (1, 1), 4:2:2 (2, 1) or 4:2:0 (2, 2) -- the template arguments of a front kernel
+template <typename F>
+static void front_with_sampling(const Geom& g, F&& f) {
+    using One = std::integral_constant<int, 1>;
+    using Two = std::integral_constant<int, 2>;
+    if (g.hr == 1)
+        f(One{}, One{});
+    else if (g.vr == 1)
+        f(Two{}, One{});
+    else
+        f(Two{}, Two{});
 }
 
 }  // namespace dmmt

@@ -20,6 +20,7 @@
 
 #include "dct_quant.hpp"
 #include "device_common.hpp"
+#include "front_common.hpp"
 #include "front_launch.hpp"
 #include "jpeg_common.hpp"
 #include "kernels.hpp"
@@ -33,39 +34,18 @@ struct YccArgs {
     const uint8_t *p0, *p1, *p2;  // Y; Cb or the pairs; Cr (planar only)
     YccDesc d;
 };
-struct YccMem {
-    const uint8_t* base;
-    __device__ __forceinline__ void load16(long long off, uint32_t (&w)[4]) const {
-        const uint4 v = ld16_nt(base + off);
-        w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
-    }
-    __device__ __forceinline__ uint32_t load1(long long off) const { return base[off]; }
-    __device__ __forceinline__ uint32_t base_lo() const { return (uint32_t)(uintptr_t)base; }
-};
 struct YccMems {
     const uint8_t *p0, *p1, *p2;
-    __device__ __forceinline__ YccMem plane(int p) const { return YccMem{p == 0 ? p0 : (p == 1 ? p1 : p2)}; }
+    __device__ __forceinline__ PlaneMem plane(int p) const { return PlaneMem{p == 0 ? p0 : (p == 1 ? p1 : p2)}; }
 };
-
-// N words from byte offset `off` (any alignment) of the 16-byte aligned LDS array
-// s: the N + 1 aligned words that hold them, funnel-shifted (v_alignbyte_b32).
-// Reads at most 3 bytes past the N words.
-template <int N>
-__device__ __forceinline__ void lds_words(const uint8_t* s, int off, uint32_t (&o)[N]) {
-    const uint32_t* a = reinterpret_cast<const uint32_t*>(s + (off & ~3));
-    uint32_t t[N + 1];
-#pragma unroll
-    for (int i = 0; i <= N; ++i) t[i] = a[i];
-#pragma unroll
-    for (int i = 0; i < N; ++i) o[i] = __builtin_amdgcn_alignbyte(t[i + 1], t[i], (uint32_t)off & 3u);
-}
 
 // One workgroup (256 threads) per tile = TM horizontally adjacent MCUs of one MCU
 // row (256 luma columns, 8 * VR luma rows), a grid-stride loop over the frame's
 // tiles (blockIdx.y = frame) with the next tile's bytes prefetched into registers
-// while this one computes -- k_front's shape (kernels.hip, front_body), with the
-// same LDS layout of the row-transformed blocks (sT, blk_base) and the same
-// emission-order index el, so the coefficients land where k_front puts them.
+// while this one computes -- k_front's shape, from the same pieces
+// (front_common.hpp): FrontGeom's LDS layout of the row-transformed blocks (sT,
+// blk_base), front_stage, and front_column_pass with its emission-order index, so
+// the coefficients land where k_front puts them.
 //  staging  YccTile / ycc_tile_chunk (ycc_load.hpp): 8 * VR luma tile rows and 8
 //     chroma tile rows per chroma plane, each at its own pitch and misalignment;
 //     past the rectangle luma stages as 0 and chroma as 0x80
@@ -77,11 +57,10 @@ __device__ __forceinline__ void lds_words(const uint8_t* s, int off, uint32_t (&
 //     half of both rows; here the samples are bytes in LDS and each thread reads
 //     the row it transforms.)  NV: a row of pairs, de-interleaved while unpacking;
 //     VU (Cr first) is a template parameter
-//  C, D  as k_front's integer-sample path: column pass, quantize_col8_scaled, one
-//     16-byte store per lane.  Samples are integers in [0, 255], the DCT's inputs
-//     integers in [-128, 127]: the bound of dct_quant.hpp's integer-sample argument
-//     holds with room to spare (|DC| = |sum| / 8 <= 1024, |AC| <= (1/4) * 64 * 128 =
-//     2048, to within a few ulps), so with q >= 1 `as i16` cannot saturate; no NaN
+//  C, D  front_column_pass, k_front's integer-sample path.  Samples are integers in
+//     [0, 255], the DCT's inputs integers in [-128, 127]: the bound of
+//     dct_quant.hpp's integer-sample argument holds with room to spare (|DC| =
+//     |sum| / 8 <= 1024, |AC| <= (1/4) * 64 * 128 = 2048, to within a few ulps), so with q >= 1 `as i16` cannot saturate; no NaN
 //     can arise (nan_possible = false), and no sample can exceed a maxval: the
 //     kernel raises no status.
 // WPE: see front_ycc_wpe below.
@@ -94,36 +73,22 @@ __device__ __forceinline__ void front_ycc_body(const YccArgs& ya, size_t frame_s
     constexpr bool NV = FMT != YCC_PLANAR;
     constexpr int VU = FMT == YCC_NV_VU ? 1 : 0;
     using T = YccTile<HR, VR, NV>;
-    constexpr int TM = 32 / HR;      // MCUs per tile
-    constexpr int ROWS = 8 * VR;     // luma rows per tile
-    constexpr int NLUMA = HR * VR;
-    constexpr int BPM = NLUMA + 2;
-    constexpr int NB = TM * BPM;     // blocks per tile
-    constexpr int NYB = 32 * VR;     // Y blocks: 32 columns x VR rows
-    constexpr int CB = TM;           // chroma blocks per component
-    constexpr int BS = 72;           // LDS floats per block (front_body)
-    auto blk_base = [](int b) { return b * BS + 4 * (((b >> 2) ^ (b >= NYB + CB ? 1 : 0)) & 1); };  // (front_body)
-    constexpr int SP = HR;           // threads per (chroma row, chroma block): one per luma block column
+    using G = FrontGeom<HR, VR>;  // the tile's blocks (front_common.hpp)
+    constexpr int NYB = G::NYB, CB = G::CB;
+    constexpr int SP = HR;  // threads per (chroma row, chroma block): one per luma block column
     static_assert(8 * CB * SP == 256, "one phase-A job per thread");
-    constexpr int NCJ = NB * 8;      // column jobs
-    constexpr int JPT = (NCJ + 255) / 256;
 
-    __shared__ __attribute__((aligned(16))) float sT[NB * BS + 4];
+    __shared__ __attribute__((aligned(16))) float sT[G::ST_FLOATS];
     __shared__ __attribute__((aligned(16))) uint8_t sRaw[T::BYTES + 16];  // (+ 16: lds_words reads 3 bytes past a row)
     __shared__ float sQ[128];
-    __shared__ float sRQ[128];  // fl(scale_row * fl(1/q))
+    __shared__ float sRQ[128];
 
     const int tid = threadIdx.x;
     const int frame = blockIdx.y;
     const size_t foff = (size_t)frame * frame_stride;  // the same offset in every plane
     const YccMems ms{ya.p0 + foff, ya.p1 + foff, ya.p2 + foff};  // (NV: p2 = p1)
     const YccDesc& d = ya.d;
-    if (tid < 128) sQ[tid] = qtab[tid];
-    if (tid < 128) sRQ[tid] = c_arai_scale[(tid >> 3) & 7] * (1.0f / qtab[tid]);
-    const int col = tid & 7;  // the column pass always handles column tid & 7
-
-    const int tiles_per_row = (g.mcux + TM - 1) / TM;
-    const int ntiles = tiles_per_row * g.mcuy;
+    front_fill_qtabs<G, true>(qtab, sQ, sRQ, tid);
 
     uint4 raw[T::NQ];
     auto load_tile = [&](int tx0, int ty0) {
@@ -136,30 +101,25 @@ __device__ __forceinline__ void front_ycc_body(const YccArgs& ya, size_t frame_s
             raw[i] = make_uint4(w[0], w[1], w[2], w[3]);
         }
     };
+    const int tiles_per_row = (g.mcux + G::TM - 1) / G::TM;
+    const int ntiles = tiles_per_row * g.mcuy;
     if ((int)blockIdx.x < ntiles) {
         const int my = blockIdx.x / tiles_per_row;
-        load_tile((blockIdx.x - my * tiles_per_row) * 256, my * ROWS);
+        load_tile((blockIdx.x - my * tiles_per_row) * 256, my * G::ROWS);
     }
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int my = tile / tiles_per_row;
-        const int mx0 = (tile - my * tiles_per_row) * TM;
-        const int x0 = mx0 * 8 * HR;
-        const int y0 = my * ROWS;
-
-#pragma unroll
-        for (int i = 0; i < T::NQ; ++i) {
-            const int q = tid + 256 * i;
-            if (q < T::NCHUNK) reinterpret_cast<uint4*>(sRaw)[q] = raw[i];
-        }
+        const int mx0 = (tile - my * tiles_per_row) * G::TM;
+        const int x0 = mx0 * 8 * G::HR, y0 = my * G::ROWS;
+        front_stage<T::NCHUNK>(sRaw, tid, raw);
         __syncthreads();
         {  // prefetch the next tile's bytes; they land while this tile computes
             const int nt = tile + gridDim.x;
             if (nt < ntiles) {
                 const int ny = nt / tiles_per_row;
-                load_tile((nt - ny * tiles_per_row) * 256, ny * ROWS);
+                load_tile((nt - ny * tiles_per_row) * 256, ny * G::ROWS);
             }
         }
-
         // ---- A: level shift + row pass (arai.rs:97-99)
         {
             const int h = tid % SP, job = tid / SP;
@@ -175,7 +135,7 @@ __device__ __forceinline__ void front_ycc_body(const YccArgs& ya, size_t frame_s
 #pragma unroll
                 for (int k = 0; k < 8; ++k) v[k] = (float)((w[k >> 2] >> (8 * (k & 3))) & 0xFFu) - 128.0f;
                 arai8(v);
-                float4* o = reinterpret_cast<float4*>(sT + blk_base((ly >> 3) * 32 + c * HR + h) + (ly & 7) * 8);
+                float4* o = reinterpret_cast<float4*>(sT + G::blk_base((ly >> 3) * 32 + c * HR + h) + (ly & 7) * 8);
                 o[0] = make_float4(v[0], v[1], v[2], v[3]);
                 o[1] = make_float4(v[4], v[5], v[6], v[7]);
             }
@@ -200,53 +160,13 @@ __device__ __forceinline__ void front_ycc_body(const YccArgs& ya, size_t frame_s
                     for (int k = 0; k < 8; ++k) v[k] = (float)((w[k >> 2] >> (8 * (k & 3))) & 0xFFu) - 128.0f;
                 }
                 arai8(v);
-                float4* o = reinterpret_cast<float4*>(sT + blk_base(NYB + comp * CB + c) + r * 8);
+                float4* o = reinterpret_cast<float4*>(sT + G::blk_base(NYB + comp * CB + c) + r * 8);
                 o[0] = make_float4(v[0], v[1], v[2], v[3]);
                 o[1] = make_float4(v[4], v[5], v[6], v[7]);
             }
         }
         __syncthreads();
-
-        // ---- C: column pass (stride 8, arai.rs:100-102), quantise (quantizer.rs:53-62)
-        // ---- D: the tile's blocks in MCU emission order (block_entangler.rs:69-77,
-        //      block_fold_iterator.rs:53-148), only those of MCUs inside the image
-        const int nvalid = min(TM, g.mcux - mx0) * BPM;
-        const long long e0 = (long long)frame * g.bpf + ((long long)my * g.mcux + mx0) * BPM;
-        int16_t* const cbase = coef + e0 * 64;  // (uniform: the stores take a 32-bit lane offset)
-        static_assert(NCJ % 256 == 0, "JPT column jobs for every thread");
-#pragma unroll
-        for (int jj = 0; jj < JPT; ++jj) {
-            const int blk = (tid + 256 * jj) >> 3;
-            int x[8];
-            {
-                const float* q = sQ + (blk < NYB ? 0 : 64) + col;
-                const float* rq = sRQ + (blk < NYB ? 0 : 64) + col;
-                float v[8];
-                const float* tb = sT + blk_base(blk) + col;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) v[i] = tb[i * 8];
-                arai8_unscaled(v);
-                quantize_col8_scaled(v, q, rq, false, x);
-            }
-            int el;
-            if (blk < NYB) {
-                const int by = blk / 32, bx = blk % 32;
-                el = (bx / HR) * BPM + by * HR + (bx % HR);  // TL,TR,BL,BR (block_entangler.rs:69-77)
-            } else if (blk < NYB + CB) {
-                el = (blk - NYB) * BPM + NLUMA;
-            } else {
-                el = (blk - NYB - CB) * BPM + NLUMA + 1;
-            }
-            const bool valid = el < nvalid;  // (uniform over the block's 8 lanes)
-            if constexpr (NARROW) {
-                coef_store_column_narrow(x, col, el, valid, cbase, coef_lo + e0 * 8, coef_hi + e0 * 64);
-            } else if (valid) {
-                uint32_t pk[4];  // the low halves of two coefficients per word (one v_perm_b32)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) pk[i] = __builtin_amdgcn_perm((uint32_t)x[2 * i + 1], (uint32_t)x[2 * i], 0x05040100u);
-                *reinterpret_cast<uint4*>(cbase + (el * 64 + 8 * col)) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-            }
-        }
+        front_column_pass<G, NARROW, false>(sT, sQ, sRQ, tid, false, g, frame, mx0, my, coef, coef_lo, coef_hi);
     }
 }
 
@@ -271,30 +191,14 @@ __global__ __launch_bounds__(256, WPE) void k_front_ycc_n(YccArgs ya, size_t fra
 // at least four resident workgroups per CU, as k_front's u8 4:4:4 and 4:2:2.
 constexpr int front_ycc_wpe() { return 4; }
 
-template <int HR, int VR, int FMT>
-static void front_ycc_impl(const YccArgs& ya, size_t frame_stride, int n_frames, const Geom& g, const Work& w,
-                           hipStream_t st, int per_cu_cap) {
-    constexpr int TM = 32 / HR;
-    const long long ntiles = (long long)((g.mcux + TM - 1) / TM) * g.mcuy;
-    if (w.coef_lo) {
-        static const FrontCfg cfgn = [] { return front_cfg(k_front_ycc_n<HR, VR, FMT, front_ycc_wpe()>); }();
-        hipLaunchKernelGGL((k_front_ycc_n<HR, VR, FMT, front_ycc_wpe()>), front_grid(cfgn, ntiles, n_frames, per_cu_cap),
-                           dim3(256), 0, st, ya, frame_stride, g, w.qtab, w.coef, w.coef_lo, w.coef_hi);
-        return;
-    }
-    static const FrontCfg cfg = [] { return front_cfg(k_front_ycc<HR, VR, FMT, front_ycc_wpe()>); }();
-    hipLaunchKernelGGL((k_front_ycc<HR, VR, FMT, front_ycc_wpe()>), front_grid(cfg, ntiles, n_frames, per_cu_cap),
-                       dim3(256), 0, st, ya, frame_stride, g, w.qtab, w.coef);
-}
 template <int FMT>
 static void front_ycc_sub(const YccArgs& ya, size_t frame_stride, int n_frames, const Geom& g, const Work& w,
                           hipStream_t st, int per_cu_cap) {
-    if (g.hr == 1)
-        front_ycc_impl<1, 1, FMT>(ya, frame_stride, n_frames, g, w, st, per_cu_cap);
-    else if (g.vr == 1)
-        front_ycc_impl<2, 1, FMT>(ya, frame_stride, n_frames, g, w, st, per_cu_cap);
-    else
-        front_ycc_impl<2, 2, FMT>(ya, frame_stride, n_frames, g, w, st, per_cu_cap);
+    front_with_sampling(g, [&](auto hr, auto vr) {
+        constexpr int HR = decltype(hr)::value, VR = decltype(vr)::value, WPE = front_ycc_wpe();
+        front_launch<k_front_ycc<HR, VR, FMT, WPE>, k_front_ycc_n<HR, VR, FMT, WPE>>(
+            g, n_frames, per_cu_cap, st, w.coef_lo, w.coef_hi, ya, frame_stride, g, w.qtab, w.coef);
+    });
 }
 
 static int ycc_chroma_width(int width, int hr) { return (width + hr - 1) / hr; }

@@ -33,6 +33,7 @@
 
 #include "dct_quant.hpp"
 #include "device_common.hpp"
+#include "front_common.hpp"
 #include "front_launch.hpp"
 #include "jpeg_common.hpp"
 #include "kernels.hpp"
@@ -155,14 +156,6 @@ struct RawTile {
             }
         }
     }
-
-    __device__ static __forceinline__ void stage(uint8_t* sRaw, int tid, const uint4 (&v)[NQ]) {
-#pragma unroll
-        for (int i = 0; i < NQ; ++i) {
-            const int q = tid + 256 * i;
-            if (q < NCHUNK) reinterpret_cast<uint4*>(sRaw)[q] = v[i];
-        }
-    }
 };
 
 // Raw pixel staging of a surface (dmmt_device_surfaces): rows row_pitch bytes
@@ -176,14 +169,6 @@ template <int LAY>
 struct SurfLayout {
     static constexpr int NPL = LAY == LAY_PLANAR ? 3 : 1;                        // planes
     static constexpr int SPP = LAY == LAY_RGBX ? 4 : (LAY == LAY_PLANAR ? 1 : 3);  // samples per pixel of a plane
-};
-struct SurfMem {
-    const uint8_t* base;
-    __device__ __forceinline__ void load16(long long off, uint32_t (&w)[4]) const {
-        const uint4 v = ld16_nt(base + off);
-        w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
-    }
-    __device__ __forceinline__ uint32_t load1(long long off) const { return base[off]; }
 };
 template <typename Sample, int ROWS, int LAY>
 struct SurfTile {
@@ -238,19 +223,11 @@ struct SurfTile {
             const int row = tr / NPL, p = tr - (tr / NPL) * NPL;
             const int py = y0 + row;
             if (q >= NCHUNK || py >= g.height) continue;
-            const SurfMem m{plane(pl, p)};
+            const PlaneMem m{plane(pl, p)};
             uint32_t w[4];
             surf_load_chunk(m, surf_row_start(sa.pitch, BPP, x0, py), misalign32(m.base, sa, x0, py), rowbytes, sa.span,
                             j, w);
             v[i] = make_uint4(w[0], w[1], w[2], w[3]);
-        }
-    }
-
-    __device__ static __forceinline__ void stage(uint8_t* sRaw, int tid, const uint4 (&v)[NQ]) {
-#pragma unroll
-        for (int i = 0; i < NQ; ++i) {
-            const int q = tid + 256 * i;
-            if (q < NCHUNK) reinterpret_cast<uint4*>(sRaw)[q] = v[i];
         }
     }
 };
@@ -258,7 +235,9 @@ struct SurfTile {
 // One workgroup (256 threads) per tile = TM horizontally adjacent MCUs of one
 // MCU row (256 padded pixel columns, 8*VR rows), looping over the frame's tiles
 // (grid = resident workgroups; blockIdx.y = frame) with the next tile's pixels
-// prefetched into registers while the current one computes.
+// prefetched into registers while the current one computes.  The tile's block
+// geometry, the staging copy and phases C and D are front_common.hpp's (FrontGeom,
+// front_stage, front_column_pass), shared with k_front_ycc and k_front_gray.
 //  A  colour + subsampling + row DCT, fused: one thread per (chroma row, luma
 //     block column) converts its 8 x VR pixels (raw bytes from LDS), box-averages
 //     the chroma in the reference's sum order and runs the row pass of its VR
@@ -287,22 +266,9 @@ __device__ __forceinline__ void front_body(const Sample* __restrict__ rgb, size_
                                            int16_t* __restrict__ coef, int* __restrict__ status,
                                            int16_t* __restrict__ coef_lo = nullptr,
                                            int8_t* __restrict__ coef_hi = nullptr) {
-    static_assert(!NARROW || sizeof(Sample) != 4, "Image<f32> dots are unbounded: wide blocks");
-    constexpr int TM = 32 / HR;      // MCUs per tile
-    constexpr int ROWS = 8 * VR;     // pixel rows per tile
-    constexpr int NLUMA = HR * VR;
-    constexpr int BPM = NLUMA + 2;
-    constexpr int NB = TM * BPM;     // blocks per tile
-    constexpr int NYB = 32 * VR;     // Y blocks: 32 columns x VR rows
-    constexpr int CB = TM;           // chroma blocks per component
-    constexpr int BS = 72;           // LDS floats per block: 64 + pad (conflict-free column reads)
-    // Block b starts at b * BS + 4 * f(b), f(b) = bit 2 of b, flipped for Cr: the
-    // 16-byte row stores of phase A (ds_write_b128, lanes in groups of 8 on 8
-    // consecutive blocks -- and Cb next to Cr with 4:2:x) start on 8 distinct
-    // 4-bank offsets mod 32, and the column reads of phase C (32 lanes = 4
-    // consecutive blocks x 8 columns) still hit 32 distinct banks.  With the plain
-    // stride the stores were 2-way conflicted.
-    auto blk_base = [](int b) { return b * BS + 4 * (((b >> 2) ^ (b >= NYB + CB ? 1 : 0)) & 1); };
+    using G = FrontGeom<HR, VR>;  // the tile's blocks (front_common.hpp)
+    constexpr int ROWS = G::ROWS, NYB = G::NYB, CB = G::CB;
+    auto blk_base = [](int b) { return G::blk_base(b); };
     constexpr int SP = HR;           // threads per (chroma row, chroma block): one per luma block column
     constexpr int NJ = 8 * CB * SP;  // fused jobs (chroma row, chroma block, luma block column): 256
     constexpr int NCS = 8 / SP;      // chroma samples of a job
@@ -311,16 +277,14 @@ __device__ __forceinline__ void front_body(const Sample* __restrict__ rgb, size_
     constexpr int SPP = SurfLayout<LAY>::SPP;
     constexpr int PXB = 8 * SPP * SB;  // raw bytes of one job row (8 pixels) in a plane
     constexpr int PXW = PXB / 4;
-    constexpr int NCJ = NB * 8;      // column jobs
-    constexpr int JPT = (NCJ + 255) / 256;
     using Raw = std::conditional_t<LAY == LAY_TIGHT, RawTile<Sample, ROWS>, SurfTile<Sample, ROWS, LAY>>;
 
     // row-transformed blocks (A -> C)
-    __shared__ __attribute__((aligned(16))) float sT[NB * BS + 4];
+    __shared__ __attribute__((aligned(16))) float sT[G::ST_FLOATS];
     __shared__ __attribute__((aligned(16))) uint8_t sRaw[Raw::BYTES];
     __shared__ float sLut[256];
     __shared__ float sQ[128];
-    __shared__ float sRQ[128];  // 1/q, correctly rounded; integer samples: fl(scale_row * fl(1/q))
+    __shared__ float sRQ[128];
 
     DMMT_TRACE_START;
     const int tid = threadIdx.x;
@@ -335,13 +299,8 @@ __device__ __forceinline__ void front_body(const Sample* __restrict__ rgb, size_
     } else {
         foff = (size_t)frame * frame_stride;
     }
-    if (tid < 128) sQ[tid] = qtab[tid];
-    if (tid < 128) sRQ[tid] = SB == 4 ? 1.0f / qtab[tid] : c_arai_scale[(tid >> 3) & 7] * (1.0f / qtab[tid]);
+    front_fill_qtabs<G, SB != 4>(qtab, sQ, sRQ, tid);
     if (SB == 1) sLut[tid] = norm_lut[tid];
-    const int col = tid & 7;  // the column pass always handles column tid & 7
-
-    const int tiles_per_row = (g.mcux + TM - 1) / TM;
-    const int ntiles = tiles_per_row * g.mcuy;
     int bad = 0;
     const bool check_range = SB != 4 && g.maxval < (SB == 1 ? 255 : 65535);
 
@@ -352,23 +311,25 @@ __device__ __forceinline__ void front_body(const Sample* __restrict__ rgb, size_
         else
             Raw::load(sa, foff, g, tx0, ty0, tid, raw);
     };
+    const int tiles_per_row = (g.mcux + G::TM - 1) / G::TM;
+    const int ntiles = tiles_per_row * g.mcuy;
     if ((int)blockIdx.x < ntiles) {
         const int my = blockIdx.x / tiles_per_row;
-        load_tile((blockIdx.x - my * tiles_per_row) * TM * 8 * HR, my * ROWS);
+        load_tile((blockIdx.x - my * tiles_per_row) * 256, my * G::ROWS);
     }
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int my = tile / tiles_per_row;
-        const int mx0 = (tile - my * tiles_per_row) * TM;
+        const int mx0 = (tile - my * tiles_per_row) * G::TM;
         const int x0 = mx0 * 8 * HR;
         const int y0 = my * ROWS;
 
-        Raw::stage(sRaw, tid, raw);
+        front_stage<Raw::NCHUNK>(sRaw, tid, raw);
         __syncthreads();
         {  // prefetch the next tile's pixels; they land while this tile computes
             const int nt = tile + gridDim.x;
             if (nt < ntiles) {
                 const int ny = nt / tiles_per_row;
-                load_tile((nt - ny * tiles_per_row) * TM * 8 * HR, ny * ROWS);
+                load_tile((nt - ny * tiles_per_row) * 256, ny * G::ROWS);
             }
         }
 
@@ -528,52 +489,7 @@ __device__ __forceinline__ void front_body(const Sample* __restrict__ rgb, size_
         }
         __syncthreads();
         DMMT_TRACE(0);
-
-        // ---- C: column pass (stride 8, arai.rs:100-102), quantise (quantizer.rs:53-62)
-        // ---- D: the tile's blocks in MCU emission order (block_entangler.rs:69-77,
-        //      block_fold_iterator.rs:53-148), only those of MCUs inside the image
-        const int nvalid = min(TM, g.mcux - mx0) * BPM;
-        const long long e0 = (long long)frame * g.bpf + ((long long)my * g.mcux + mx0) * BPM;
-        int16_t* const cbase = coef + e0 * 64;  // (uniform: the stores take a 32-bit lane offset)
-        static_assert(NCJ % 256 == 0, "JPT column jobs for every thread");
-#pragma unroll
-        for (int jj = 0; jj < JPT; ++jj) {
-            const int blk = (tid + 256 * jj) >> 3;
-            int x[8];
-            {
-                const float* q = sQ + (blk < NYB ? 0 : 64) + col;
-                const float* rq = sRQ + (blk < NYB ? 0 : 64) + col;
-                float v[8];
-                const float* tb = sT + blk_base(blk) + col;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) v[i] = tb[i * 8];
-                if constexpr (SB == 4) {  // Image<f32> dots: unbounded coefficients
-                    arai8(v);
-                    quantize_col8(v, q, rq, x);
-                } else {
-                    arai8_unscaled(v);
-                    quantize_col8_scaled(v, q, rq, g.maxval == 0, x);
-                }
-            }
-            int el;
-            if (blk < NYB) {
-                const int by = blk / 32, bx = blk % 32;
-                el = (bx / HR) * BPM + by * HR + (bx % HR);  // TL,TR,BL,BR (block_entangler.rs:69-77)
-            } else if (blk < NYB + CB) {
-                el = (blk - NYB) * BPM + NLUMA;
-            } else {
-                el = (blk - NYB - CB) * BPM + NLUMA + 1;
-            }
-            const bool valid = el < nvalid;  // (uniform over the block's 8 lanes)
-            if constexpr (NARROW) {
-                coef_store_column_narrow(x, col, el, valid, cbase, coef_lo + e0 * 8, coef_hi + e0 * 64);
-            } else if (valid) {
-                uint32_t pk[4];  // the low halves of two coefficients per word (one v_perm_b32)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) pk[i] = __builtin_amdgcn_perm((uint32_t)x[2 * i + 1], (uint32_t)x[2 * i], 0x05040100u);
-                *reinterpret_cast<uint4*>(cbase + (el * 64 + 8 * col)) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-            }
-        }
+        front_column_pass<G, NARROW, SB == 4>(sT, sQ, sRQ, tid, g.maxval == 0, g, frame, mx0, my, coef, coef_lo, coef_hi);
         DMMT_TRACE(2);
     }
 
@@ -1701,56 +1617,39 @@ constexpr int front_wpe() {
     return sizeof(S) == 1 ? (HR * VR == 4 ? FRONT_WPE_420 : 4) : 1;
 }
 
-// (the resident grid of an instantiation: FrontCfg, front_cfg, front_grid of
-// front_launch.hpp)
+// (the launch and its resident grid: front_launch, front_with_sampling of
+// front_launch.hpp; float samples have no narrow twin)
 
-template <int HR, int VR, typename S>
-static void front_impl(const void* rgb, size_t stride_elems, int n_frames, const Geom& g, const Work& w,
-                       hipStream_t st, int per_cu_cap) {
-    constexpr int TM = 32 / HR;
-    const long long ntiles = (long long)((g.mcux + TM - 1) / TM) * g.mcuy;
-    if constexpr (sizeof(S) != 4) {
-        if (w.coef_lo) {
-            static const FrontCfg cfgn = [] { return front_cfg(k_front_n<HR, VR, S, front_wpe<HR, VR, S>()>); }();
-            hipLaunchKernelGGL((k_front_n<HR, VR, S, front_wpe<HR, VR, S>()>),
-                               front_grid(cfgn, ntiles, n_frames, per_cu_cap), dim3(256), 0, st, (const S*)rgb,
-                               stride_elems, g, w.norm_lut, w.qtab, w.coef, w.status, w.coef_lo, w.coef_hi);
-            return;
-        }
-    }
-    static const FrontCfg cfg = [] { return front_cfg(k_front<HR, VR, S, front_wpe<HR, VR, S>()>); }();
-    hipLaunchKernelGGL((k_front<HR, VR, S, front_wpe<HR, VR, S>()>), front_grid(cfg, ntiles, n_frames, per_cu_cap),
-                       dim3(256), 0, st, (const S*)rgb, stride_elems, g, w.norm_lut, w.qtab, w.coef, w.status);
+template <typename S>
+static void front_sub(const void* rgb, size_t stride_elems, int n_frames, const Geom& g, const Work& w, hipStream_t st,
+                      int per_cu_cap) {
+    front_with_sampling(g, [&](auto hr, auto vr) {
+        constexpr int HR = decltype(hr)::value, VR = decltype(vr)::value, WPE = front_wpe<HR, VR, S>();
+        if constexpr (sizeof(S) == 4)
+            front_launch<k_front<HR, VR, S, WPE>, nullptr>(g, n_frames, per_cu_cap, st, w.coef_lo, w.coef_hi,
+                                                           (const S*)rgb, stride_elems, g, w.norm_lut, w.qtab, w.coef,
+                                                           w.status);
+        else
+            front_launch<k_front<HR, VR, S, WPE>, k_front_n<HR, VR, S, WPE>>(g, n_frames, per_cu_cap, st, w.coef_lo,
+                                                                             w.coef_hi, (const S*)rgb, stride_elems, g,
+                                                                             w.norm_lut, w.qtab, w.coef, w.status);
+    });
 }
 
-template <int HR, int VR, typename S, int LAY>
-static void front_surf_impl(const SurfArgs& sa, size_t frame_stride, int n_frames, const Geom& g, const Work& w,
-                            hipStream_t st, int per_cu_cap) {
-    constexpr int TM = 32 / HR;
-    const long long ntiles = (long long)((g.mcux + TM - 1) / TM) * g.mcuy;
-    if constexpr (sizeof(S) != 4) {
-        if (w.coef_lo) {
-            static const FrontCfg cfgn = [] { return front_cfg(k_front_surf_n<HR, VR, S, LAY, front_wpe<HR, VR, S>()>); }();
-            hipLaunchKernelGGL((k_front_surf_n<HR, VR, S, LAY, front_wpe<HR, VR, S>()>),
-                               front_grid(cfgn, ntiles, n_frames, per_cu_cap), dim3(256), 0, st, sa, frame_stride, g,
-                               w.norm_lut, w.qtab, w.coef, w.status, w.coef_lo, w.coef_hi);
-            return;
-        }
-    }
-    static const FrontCfg cfg = [] { return front_cfg(k_front_surf<HR, VR, S, LAY, front_wpe<HR, VR, S>()>); }();
-    hipLaunchKernelGGL((k_front_surf<HR, VR, S, LAY, front_wpe<HR, VR, S>()>),
-                       front_grid(cfg, ntiles, n_frames, per_cu_cap), dim3(256), 0, st, sa, frame_stride, g, w.norm_lut,
-                       w.qtab, w.coef, w.status);
-}
 template <typename S, int LAY>
 static void front_surf_sub(const SurfArgs& sa, size_t frame_stride, int n_frames, const Geom& g, const Work& w,
                            hipStream_t st, int per_cu_cap) {
-    if (g.hr == 1)
-        front_surf_impl<1, 1, S, LAY>(sa, frame_stride, n_frames, g, w, st, per_cu_cap);
-    else if (g.vr == 1)
-        front_surf_impl<2, 1, S, LAY>(sa, frame_stride, n_frames, g, w, st, per_cu_cap);
-    else
-        front_surf_impl<2, 2, S, LAY>(sa, frame_stride, n_frames, g, w, st, per_cu_cap);
+    front_with_sampling(g, [&](auto hr, auto vr) {
+        constexpr int HR = decltype(hr)::value, VR = decltype(vr)::value, WPE = front_wpe<HR, VR, S>();
+        if constexpr (sizeof(S) == 4)
+            front_launch<k_front_surf<HR, VR, S, LAY, WPE>, nullptr>(g, n_frames, per_cu_cap, st, w.coef_lo, w.coef_hi,
+                                                                     sa, frame_stride, g, w.norm_lut, w.qtab, w.coef,
+                                                                     w.status);
+        else
+            front_launch<k_front_surf<HR, VR, S, LAY, WPE>, k_front_surf_n<HR, VR, S, LAY, WPE>>(
+                g, n_frames, per_cu_cap, st, w.coef_lo, w.coef_hi, sa, frame_stride, g, w.norm_lut, w.qtab, w.coef,
+                w.status);
+    });
 }
 
 // samples per pixel of a plane, 0: a (format, sample_bytes) pair outside the supported matrix
@@ -1791,28 +1690,12 @@ hipError_t launch_front_surface(const Surface& sf, size_t frame_stride_bytes, in
 hipError_t launch_front(const void* rgb, size_t frame_stride_bytes, int sample_bytes, int n_frames, const Geom& g,
                         const Work& w, hipStream_t st, int per_cu_cap) {
     const size_t se = frame_stride_bytes / (size_t)sample_bytes;
-    if (sample_bytes == 4) {
-        if (g.hr == 1)
-            front_impl<1, 1, float>(rgb, se, n_frames, g, w, st, per_cu_cap);
-        else if (g.vr == 1)
-            front_impl<2, 1, float>(rgb, se, n_frames, g, w, st, per_cu_cap);
-        else
-            front_impl<2, 2, float>(rgb, se, n_frames, g, w, st, per_cu_cap);
-    } else if (sample_bytes == 1) {
-        if (g.hr == 1)
-            front_impl<1, 1, uint8_t>(rgb, se, n_frames, g, w, st, per_cu_cap);
-        else if (g.vr == 1)
-            front_impl<2, 1, uint8_t>(rgb, se, n_frames, g, w, st, per_cu_cap);
-        else
-            front_impl<2, 2, uint8_t>(rgb, se, n_frames, g, w, st, per_cu_cap);
-    } else {
-        if (g.hr == 1)
-            front_impl<1, 1, uint16_t>(rgb, se, n_frames, g, w, st, per_cu_cap);
-        else if (g.vr == 1)
-            front_impl<2, 1, uint16_t>(rgb, se, n_frames, g, w, st, per_cu_cap);
-        else
-            front_impl<2, 2, uint16_t>(rgb, se, n_frames, g, w, st, per_cu_cap);
-    }
+    if (sample_bytes == 4)
+        front_sub<float>(rgb, se, n_frames, g, w, st, per_cu_cap);
+    else if (sample_bytes == 1)
+        front_sub<uint8_t>(rgb, se, n_frames, g, w, st, per_cu_cap);
+    else
+        front_sub<uint16_t>(rgb, se, n_frames, g, w, st, per_cu_cap);
     return hipGetLastError();
 }
 
