@@ -5,14 +5,12 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
-#include <algorithm>
 #include <type_traits>
 
 #include "jpeg_common.hpp"
+#include "launch_grids.hpp"
 
 namespace dmmt {
-
-static inline int clampi(long long v, int lo, int hi) { return (int)(v < lo ? lo : (v > hi ? hi : v)); }
 
 // The resident workgroups of one front-kernel instantiation: one workgroup per
 // resident slot, each looping over tiles and prefetching the next.
@@ -36,8 +34,7 @@ static FrontCfg front_cfg(K kernel) {
 }
 // per_cu_cap: fewer resident workgroups per CU (a context of several lanes)
 static inline dim3 front_grid(const FrontCfg& cfg, long long ntiles, int n_frames, int per_cu_cap) {
-    const int res = per_cu_cap > 0 && !cfg.per_cu_env ? std::min(cfg.resident, per_cu_cap * cfg.n_cus) : cfg.resident;
-    return dim3(clampi(ntiles, 1, res / n_frames > 0 ? res / n_frames : 1), n_frames);
+    return dim3(front_grid_x(cfg.resident, cfg.n_cus, cfg.per_cu_env, ntiles, n_frames, per_cu_cap), n_frames);
 }
 
 // One launch of the instantiation Wide, or of its narrow twin Narrow (nullptr: it

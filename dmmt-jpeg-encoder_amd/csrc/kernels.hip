@@ -1716,9 +1716,7 @@ hipError_t launch_hist(int n_frames, const Geom& g, const Work& w, int check_cat
     // so a context of several lanes passes wg_cap = DMMT_HIST_WG_CAP_LANES (512:
     // settled 4-lane bench +2.4 %, profiles/r06_hist_cap_lanes_ab.txt) and one lane
     // keeps the default
-    const int cap = wg_cap > 0 ? wg_cap : DMMT_HIST_WG_CAP;
-    const int per_frame = cap / n_frames > 0 ? cap / n_frames : 1;
-    dim3 grid(clampi((g.bpf + 255) / 256, 1, per_frame), n_frames);
+    dim3 grid(hist_grid_x(g.bpf, n_frames, wg_cap > 0 ? wg_cap : DMMT_HIST_WG_CAP), n_frames);
     const bool fuse = fuse_tables && tables_fusable(g);
     auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, (const int16_t*)w.coef, w.dcdiff, w.lastnz, g, w.ac_hist,

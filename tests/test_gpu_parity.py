@@ -37,6 +37,28 @@ def test_dct_operator_matches_oracle(encoder):
     assert np.array_equal(gpu.view(np.uint32), cpu.view(np.uint32))
 
 
+def test_dct_operator_past_the_grid_cap(encoder):
+    """k_dct_blocks runs at most 2048 workgroups of 32 blocks and loops: 2 x 65536 + 17
+    blocks are two full passes and a group of 17 in a third.  Bit for bit against the
+    oracle on a subset that covers each pass, the pass boundaries, the partial group
+    and the last block, and all of them against the GPU's own single-pass results
+    (chunks of at most 65536 blocks)."""
+    full = 2048 * 32
+    n = 2 * full + 17
+    rng = np.random.default_rng(2)
+    blocks = rng.uniform(-128, 127, (n, 64)).astype(np.float32)
+    gpu = encoder.dct_transform(blocks)
+    assert gpu.shape == blocks.shape
+    pick = np.unique(np.concatenate([np.arange(0, 40), np.arange(full - 40, full + 40), np.arange(2 * full - 40, n),
+                                     rng.integers(0, full, 100), rng.integers(full, 2 * full, 100)]))
+    assert pick[0] == 0 and pick[-1] == n - 1 and ((pick >= full) & (pick < 2 * full)).sum() >= 100
+    cpu = np.stack([oracle.dct_block(blocks[i]) for i in pick])
+    assert np.array_equal(gpu[pick].view(np.uint32), cpu.view(np.uint32))
+    for a in range(0, n, full):
+        one_pass = encoder.dct_transform(blocks[a:a + full])
+        assert np.array_equal(gpu[a:a + full].view(np.uint32), one_pass.view(np.uint32)), a
+
+
 def test_dct_operator_reference_kat(encoder):  # arai.rs:190-202 vs the naive transform, 1e-4
     from test_oracle_kat import TEST_VALUES, naive_dct
     out = dmmt_jpeg.AraiDiscrete8x8CosineTransformer(encoder).transform(TEST_VALUES)
