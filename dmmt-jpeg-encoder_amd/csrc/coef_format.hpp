@@ -81,6 +81,48 @@ inline bool coef_narrow_for(int mode, int sample_bytes, const uint8_t* luma_q, c
     return true;
 }
 
+// k_front's escape test (DMMT_NARROW_FOLD): a column job escapes iff one of its hi
+// rows -- rows 3..7 always, of rows 0..2 those from coef_lo_rows(col) on -- holds a
+// value outside -127..127.  n: the column's values as floats (the quantiser's rintf
+// results, exact).  The largest magnitude among the hi rows: rows 0..2 through a
+// select on the column (on the device the three conditions are lane masks that do
+// not change in the kernel: col = lane & 7), then three v_max3 and a v_max with the
+// magnitudes as source modifiers.
+#ifdef __HIPCC__
+#define DMMT_CF_FN __host__ __device__ __forceinline__
+#else
+#define DMMT_CF_FN inline
+#endif
+// one row at a time (r a constant once unrolled): the running maximum m with row r of column c
+DMMT_CF_FN float coef_hi_mag_row(float m, int r, float n, int c) {
+    static_assert(coef_lo_rows(0) == 3 && coef_lo_rows(1) == 2 && coef_lo_rows(2) == 2 && coef_lo_rows(3) == 1 &&
+                      coef_lo_rows(4) == 0 && coef_lo_rows(7) == 0,
+                  "row 2 is hi from column 1 on, row 1 from column 3 on, row 0 from column 4 on");
+    const float a = __builtin_fabsf(n);
+    const bool hi = r >= 3 || c >= (r == 0 ? 4 : r == 1 ? 3 : 1);
+    return __builtin_fmaxf(m, hi ? a : 0.0f);
+}
+DMMT_CF_FN float coef_hi_mag(const float (&n)[8], int c) {
+    float m = 0.0f;
+    for (int r = 0; r < 8; ++r) m = coef_hi_mag_row(m, r, n[r], c);
+    return m;
+}
+constexpr float kCoefHiMagMax = 127.0f;  // a larger coef_hi_mag: the column escapes
+// host model of the test on the int16 column x (rows 0..7) of column c
+inline bool coef_column_escapes(const int16_t* x, int c) {
+    float n[8];
+    for (int r = 0; r < 8; ++r) n[r] = (float)x[r];
+    return coef_hi_mag(n, c) > kCoefHiMagMax;
+}
+
+#ifndef DMMT_NARROW_FOLD
+// k_front's narrow store: one folded range test, clamps only in a wave with an escape.
+// Off in the product: alone it measured level with or below the clamps on the 4-lane
+// 4K bench (profiles/STUDIES.md section K); `make VARIANT=x EXTRA=-DDMMT_NARROW_FOLD=1`
+// builds it.
+#define DMMT_NARROW_FOLD 0
+#endif
+
 #ifdef __HIPCC__
 // true when a byte of w is 0x80
 __device__ __forceinline__ bool coef_word_escapes(uint32_t w) {
@@ -92,30 +134,51 @@ __device__ __forceinline__ bool coef_word_escapes(uint32_t w) {
 // column's 8 quantised values x (rows 0..7).  Every lane of the wave calls it (the
 // lo values travel to the block's col-0 lane over DPP row shifts); `valid` is
 // uniform over a block's lanes.  el: the block's index from the three (uniform)
-// bases.
-__device__ __forceinline__ void coef_store_column_narrow(const int (&x)[8], int col, int el, bool valid,
+// bases.  FOLD: `esc_fold` is the lane's escape test (coef_hi_mag of the column above
+// kCoefHiMagMax), and a wave in which no lane escapes -- nearly every one, by
+// coef_narrow_for -- packs the low bytes of x as they are (two's complement: the
+// value, for |v| <= 127), without the clamps and the test on the packed words.
+template <bool FOLD>
+__device__ __forceinline__ void coef_store_column_narrow(const int (&x)[8], bool esc_fold, int col, int el, bool valid,
                                                          int16_t* __restrict__ wide, int16_t* __restrict__ lo,
                                                          int8_t* __restrict__ hi) {
-    uint32_t c[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) c[i] = (uint32_t)min(max(x[i], -128), 128);  // v_med3_i32; low byte: the value or 0x80
     // byte 0 of four values per word (selector 0x0c: a zero byte)
-    uint32_t w0 = __builtin_amdgcn_perm(c[1], c[0], 0x0c0c0400u) | __builtin_amdgcn_perm(c[3], c[2], 0x04000c0cu);
-    const uint32_t w1 = __builtin_amdgcn_perm(c[5], c[4], 0x0c0c0400u) | __builtin_amdgcn_perm(c[7], c[6], 0x04000c0cu);
-    w0 &= 0xFFFFFFFFu << (8 * (col == 0 ? 3 : col < 3 ? 2 : col == 3 ? 1 : 0));  // the lo positions' bytes (coef_lo_rows)
+    auto pack4 = [](uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
+        return __builtin_amdgcn_perm(b, a, 0x0c0c0400u) | __builtin_amdgcn_perm(d, c, 0x04000c0cu);
+    };
+    const uint32_t himask = 0xFFFFFFFFu << (8 * (col == 0 ? 3 : col < 3 ? 2 : col == 3 ? 1 : 0));  // the lo positions' bytes (coef_lo_rows)
     // rows 0 and 1 of columns 1, 2, 3 to the col-0 lane (row_shl:n: lane i reads lane i + n)
     const uint32_t p = __builtin_amdgcn_perm((uint32_t)x[1], (uint32_t)x[0], 0x05040100u);
     const uint32_t s1 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)p, 0x101, 0xF, 0xF, true);
     const uint32_t s2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)p, 0x102, 0xF, 0xF, true);
     const uint32_t s3 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)p, 0x103, 0xF, 0xF, true);
-    // the block's flag: the OR of its 8 lanes' escape tests into the col-0 lane, whose
-    // byte 0 is position 0's -- from the wave's vote, and only when a lane escapes
-    const bool esc = coef_word_escapes(w0) || coef_word_escapes(w1);
-    const unsigned long long em = __builtin_amdgcn_ballot_w64(esc);
-    if (em != 0) {  // (uniform) rare
-        const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-        const uint32_t group = (uint32_t)(em >> (lane & 56u)) & 0xFFu;  // the votes of the block's 8 lanes
-        w0 |= col == 0 && group != 0u ? 1u : 0u;
+    uint32_t w0, w1;
+    bool esc;
+    unsigned long long em;
+    if (FOLD) {
+        esc = esc_fold;
+        em = __builtin_amdgcn_ballot_w64(esc);
+    }
+    if (FOLD && em == 0) {  // (uniform) nearly always
+        w0 = pack4((uint32_t)x[0], (uint32_t)x[1], (uint32_t)x[2], (uint32_t)x[3]) & himask;
+        w1 = pack4((uint32_t)x[4], (uint32_t)x[5], (uint32_t)x[6], (uint32_t)x[7]);
+    } else {
+        uint32_t c[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) c[i] = (uint32_t)min(max(x[i], -128), 128);  // v_med3_i32; low byte: the value or 0x80
+        w0 = pack4(c[0], c[1], c[2], c[3]) & himask;
+        w1 = pack4(c[4], c[5], c[6], c[7]);
+        if (!FOLD) {
+            esc = coef_word_escapes(w0) || coef_word_escapes(w1);
+            em = __builtin_amdgcn_ballot_w64(esc);
+        }
+        // the block's flag: the OR of its 8 lanes' escape tests into the col-0 lane, whose
+        // byte 0 is position 0's -- from the wave's vote, and only when a lane escapes
+        if (em != 0) {  // (uniform) rare
+            const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+            const uint32_t group = (uint32_t)(em >> (lane & 56u)) & 0xFFu;  // the votes of the block's 8 lanes
+            w0 |= col == 0 && group != 0u ? 1u : 0u;
+        }
     }
     if (valid) {
         *reinterpret_cast<uint2*>(hi + (el * 64 + 8 * col)) = make_uint2(w0, w1);

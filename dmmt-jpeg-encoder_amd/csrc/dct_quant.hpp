@@ -159,16 +159,28 @@ DMMT_DQ_FN void arai8(float (&v)[8]) {
 DMMT_DQ_FN float quant_margin(float t, float n) {
     return __builtin_fmaf(fabsf(t), DMMT_QUANT_SCALED_BAND, fabsf(t - n));  // (the product is exact: one rounding)
 }
-DMMT_DQ_FN void quantize_col8_scaled(const float (&u)[8], const float* q, const float* crq, bool nan_possible,
-                                     int (&x)[8]) {
+// FOLD: also `mag` = the eight results as floats folded row by row, mag = fold(mag,
+// r, result) from 0 -- k_front's narrow store tests the column's range on it
+// (coef_format.hpp: coef_hi_mag_row).  The rintf results are in registers before
+// their conversion, and the rare exact path folds its own results again.
+template <bool FOLD, class Fold>
+DMMT_DQ_FN void quantize_col8_scaled_impl(const float (&u)[8], const float* q, const float* crq, bool nan_possible,
+                                          int (&x)[8], const Fold& fold, float& mag) {
     float dist = 0.0f;
+    if constexpr (FOLD) mag = 0.0f;
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
         const float t = u[r] * crq[8 * r];
         const float n = __builtin_rintf(t);
         dist = fmaxf(dist, quant_margin(t, n));
         x[r] = (int)n;
+        if constexpr (FOLD) mag = fold(mag, r, n);
     }
+#ifdef __HIP_DEVICE_COMPILE__
+    // (the fold stays here: sunk past the branch below, as the compiler would have it,
+    // it keeps the eight floats alive beside x and u across the exact path)
+    if constexpr (FOLD) asm volatile("" : "+v"(mag));
+#endif
     if (nan_possible || !(dist < DMMT_QUANT_SCALED_HALF)) {
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
@@ -178,7 +190,22 @@ DMMT_DQ_FN void quantize_col8_scaled(const float (&u)[8], const float* q, const 
                 x[r] = quantize(u[r] * c_arai_scale[r], q[8 * r]);
             }
         }
+        if constexpr (FOLD) {
+            mag = 0.0f;
+#pragma unroll
+            for (int r = 0; r < 8; ++r) mag = fold(mag, r, (float)x[r]);
+        }
     }
+}
+DMMT_DQ_FN void quantize_col8_scaled(const float (&u)[8], const float* q, const float* crq, bool nan_possible,
+                                     int (&x)[8]) {
+    float mag;
+    quantize_col8_scaled_impl<false>(u, q, crq, nan_possible, x, 0, mag);
+}
+template <class Fold>
+DMMT_DQ_FN void quantize_col8_scaled_fold(const float (&u)[8], const float* q, const float* crq, bool nan_possible,
+                                          int (&x)[8], const Fold& fold, float& mag) {
+    quantize_col8_scaled_impl<true>(u, q, crq, nan_possible, x, fold, mag);
 }
 
 }  // namespace dmmt

@@ -67,6 +67,14 @@ namespace dmmt {
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
+// Data passed between the lanes of ONE wave through LDS (the tables' tail,
+// k_stuffwrite's staged pass): a wave's LDS operations complete in order, so no
+// s_barrier -- only no code motion across.
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);

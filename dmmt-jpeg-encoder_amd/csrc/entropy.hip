@@ -20,7 +20,7 @@
 //                actual alignment plus the byte it shares with the next chunk,
 //                built from the recorded edge bits), the RST marker closing a
 //                segment -- and their scan (every chunk's place in the file).
-//  k_stuffwrite  one workgroup per chunk: the bytes whose first bit lies in the
+//  k_stuffwrite  one wave per chunk: the bytes whose first bit lies in the
 //                chunk, shifted out of its staging slot (the last one built from
 //                the edge bits, 1-padded at the end of the scan), a 0x00 after
 //                every 0xFF, staged in LDS and stored coalesced after the header;
@@ -61,8 +61,6 @@ constexpr int kEmitOccBatch = kChunkBlocks == 256 ? DMMT_EMIT_OCC_BATCH : 3;
 // windows, every block copying (or, on the re-walk path, re-emitting) only the
 // words inside the window.
 constexpr int kEmitWords = 4 * kChunkBlocks;
-// Bytes per pass of k_stuffwrite (16 per thread).
-constexpr int kStuffPass = 4096;
 #ifndef DMMT_EMIT_BRANCHFREE
 #define DMMT_EMIT_BRANCHFREE 1  // SlotSink stores a word per piece, no flush branch (0: study builds)
 #endif
@@ -71,6 +69,9 @@ constexpr int kStuffPass = 4096;
 #endif
 #ifndef DMMT_TAIL_NSEG1
 #define DMMT_TAIL_NSEG1 1  // fused offsets: no chunk_span division per chunk without restart intervals (0: study builds)
+#endif
+#ifndef DMMT_STUFF_WAVE_CHUNK
+#define DMMT_STUFF_WAVE_CHUNK 1  // k_stuffwrite: one chunk per wave, no workgroup barrier (0: one per workgroup, study builds)
 #endif
 #ifndef DMMT_WALK_COLUMN_MAJOR
 #define DMMT_WALK_COLUMN_MAJOR 1  // the walk reads the column-major block's registers in place (0: permuted to zigzag order first)
@@ -1114,6 +1115,242 @@ __global__ __launch_bounds__(1024) void k_offsets(const uint32_t* __restrict__ c
 }
 
 // ----------------------------------------------------------------- k_stuffwrite
+// A thread's 16-byte piece of a pass, MSB first in x: the five slot words wv that
+// hold it, sh bits in (sh < 32); with_tail: the piece holds the chunk's shared /
+// padded last byte, byte j of it, whose value is `tail`.  ffm: bit 7 of every one
+// of the piece's nvalid bytes that is 0xFF; returns their count.
+__device__ __forceinline__ uint32_t stuff_piece(const uint32_t (&wv)[5], int sh, int nvalid, bool with_tail, int j,
+                                                uint32_t tail, uint32_t (&x)[4], uint32_t (&ffm)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) x[i] = sh ? (wv[i] << sh) | (wv[i + 1] >> (32 - sh)) : wv[i];
+    if (with_tail) {
+        const int sft = 24 - 8 * (j & 3);
+        x[j >> 2] = (x[j >> 2] & ~(0xFFu << sft)) | (tail << sft);
+    }
+    uint32_t cnt = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {  // 0xFF bytes among the valid ones
+        const int nv = min(max(nvalid - 4 * i, 0), 4);
+        const uint32_t vmask = nv ? 0x80808080u & (0xFFFFFFFFu << (32 - 8 * nv)) : 0u;
+        const uint32_t t = ~x[i];
+        const uint32_t nonzero = (((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t) & 0x80808080u;
+        ffm[i] = ~nonzero & vmask;
+        cnt += (uint32_t)__popc(ffm[i]);
+    }
+    return cnt;
+}
+
+// Stage a piece, stuffed, at sOut + dst.  No branch per byte: byte j goes to dst + j
+// + (the 0xFF bytes before it in the piece), a population count of the piece's 0xFF
+// mask, and all 16 are written -- [dst, dst + 16 + cnt) is the piece's own (the
+// caller's prefix keeps the next one clear of it), and what a partial last piece
+// writes past its valid bytes lies past the pass and is never stored.  Only the
+// pieces that hold a 0xFF (about 6 % at 4K q90) then enter one region for their
+// 0x00 bytes, a loop over the set bits (STUDIES section H).
+__device__ __forceinline__ void stuff_stage(uint8_t* sOut, uint32_t dst, const uint32_t (&x)[4], const uint32_t (&ffm)[4],
+                                            uint32_t cnt) {
+    uint32_t a = dst;  // where byte 4 i goes
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t w = x[i], f = ffm[i];
+        sOut[a + 4 * i] = (uint8_t)(w >> 24);
+        sOut[a + (uint32_t)__popc(f & 0x80000000u) + 4 * i + 1] = (uint8_t)(w >> 16);
+        sOut[a + (uint32_t)__popc(f & 0x80800000u) + 4 * i + 2] = (uint8_t)(w >> 8);
+        sOut[a + (uint32_t)__popc(f & 0x80808000u) + 4 * i + 3] = (uint8_t)w;
+        a += (uint32_t)__popc(f);
+    }
+    if (cnt) {
+        // bit j of m: byte j is 0xFF (the four flags of a word, at bits 24, 16, 8
+        // and 0 once shifted, gathered by one multiplication without carries)
+        uint32_t m = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            m |= ((((ffm[i] >> 7) * 0x08040201u) >> 24) & 0xFu) << (4 * i);
+        uint32_t z = dst + 1;  // the 0x00 of the first 0xFF byte, were it byte 0
+        while (m) {
+            sOut[z + (uint32_t)__builtin_ctz(m)] = 0x00;
+            ++z;
+            m &= m - 1u;
+        }
+    }
+}
+
+#if DMMT_STUFF_WAVE_CHUNK
+// One chunk per wave: wave w of workgroup b owns chunk 4 b + w.  Everything that is
+// uniform over a chunk -- the prologue's loads, the capacity and summary checks, the
+// chunk_span division, the shared last byte, EOI / RSTm / out_len -- runs once per
+// chunk in scalar registers, not once in each of four waves, and no wave waits for
+// another: the 0xFF prefix of a pass is the wave's own scan, the pass is staged in
+// the wave's own LDS region, and a wave's LDS writes and reads are ordered by
+// wave_lds_sync().  A pass is 64 lanes x 16 bytes.
+constexpr int kStuffWavePass = 1024;
+// the staged pass: delta < 16, kStuffWavePass bytes and as many 0x00, the last
+// piece's 16-byte writes to 16 + 15 past its start at most
+constexpr int kStuffWaveLds = 2 * kStuffWavePass + 16;
+constexpr int kStuffPre = 4;  // passes whose slot words go out with the prologue's loads (a 4K q90 chunk: about 4)
+static_assert(kStuffPre * (kStuffWavePass / 4) + 1 <= kChunkWordsCap, "the words read unasked lie inside the chunk's slot");
+
+__global__ __launch_bounds__(256, 8) void k_stuffwrite(const uint32_t* __restrict__ stage,
+                                                    const uint32_t* __restrict__ chunk_bits,
+                                                    const uint32_t* __restrict__ chunk_edge,
+                                                    const unsigned long long* __restrict__ chunk_bit0,
+                                                    const unsigned long long* __restrict__ chunk_out,
+                                                    const unsigned long long* __restrict__ total_out,
+                                                    const uint32_t* __restrict__ hdr_len, Geom g,
+                                                    uint8_t* __restrict__ out, size_t out_stride,
+                                                    uint32_t* __restrict__ out_len, int* __restrict__ status) {
+    __shared__ __attribute__((aligned(16))) uint8_t sAll[4 * kStuffWaveLds];
+    const int lane = lane_id();
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int frame = blockIdx.y;
+    const int c = 4 * (int)blockIdx.x + wave;
+    if (c >= g.nch) return;  // (the last workgroup's spare waves)
+    uint8_t* const sOut = sAll + wave * kStuffWaveLds;
+    const size_t cid = (size_t)frame * g.nch + c;
+    const bool last = c == g.nch - 1;
+    const size_t cidn = last ? cid : cid + 1;
+    // every global load of the prologue is issued before any is used: the frame's
+    // and the chunk's words, the next chunk's (its bits and edge for the shared last
+    // byte, its output offset for a closing RSTm), and this lane's slot words of the
+    // first kStuffPre passes -- pass k's are words 256 k + 4 lane on, whatever the
+    // chunk's first bit (which lies in the slot's first byte) -- so a chunk of up to
+    // kStuffPre passes costs one latency
+    const uint32_t hdr = hdr_len[frame];
+    const unsigned long long tot = total_out[frame];
+    const unsigned long long b0 = chunk_bit0[cid];
+    const uint32_t n = chunk_bits[cid], edge = chunk_edge[cid];
+    const uint32_t n_next = chunk_bits[cidn], edge_next = chunk_edge[cidn];
+    const unsigned long long cout = chunk_out[cid], cout_next = chunk_out[cidn];
+    const uint32_t* slot = stage + cid * (size_t)kChunkWordsCap;
+    uint32_t wpre[kStuffPre][5];
+#pragma unroll
+    for (int k = 0; k < kStuffPre; ++k) {
+        const uint32_t* w = slot + (kStuffWavePass / 4) * k + 4 * lane;
+        const uint4 q = *reinterpret_cast<const uint4*>(w);
+        wpre[k][0] = q.x, wpre[k][1] = q.y, wpre[k][2] = q.z, wpre[k][3] = q.w;
+        wpre[k][4] = w[4];
+    }
+    // (the compiler would sink each load to its first use, past the branches below)
+    asm volatile("" ::"s"(hdr), "s"(tot), "s"(b0), "s"(n), "s"(edge), "s"(n_next), "s"(edge_next), "s"(cout),
+                 "s"(cout_next));
+#pragma unroll
+    for (int k = 0; k < kStuffPre; ++k)
+        asm volatile("" ::"v"(wpre[k][0]), "v"(wpre[k][1]), "v"(wpre[k][2]), "v"(wpre[k][3]), "v"(wpre[k][4]));
+    const unsigned long long end = (unsigned long long)hdr + tot;
+    if (end + 2 > out_stride) {  // uniform over the frame
+        if (c == 0 && lane == 0) {
+            out_len[frame] = 0;  // reported as DMMT_E_CAPACITY by the host
+            raise_status(status, 16);
+        }
+        return;
+    }
+    // This chunk's own summary, checked before any store (a few scalar compares):
+    // its bits fit its staging slot, and its stuffed bytes -- at most two per scan
+    // byte, the closing RST marker included -- lie between its offset and the next
+    // chunk's (the frame total for the last) inside the frame's output slot.  The
+    // summaries come from k_emit and the offsets scan, so this only fires on a broken
+    // producer (the round-5 grouped-offsets timing ablation, which left the per-chunk
+    // offsets unset, stored through them and faulted:
+    // profiles/r05_grouped_offsets_ab.txt); it then raises the capacity error instead
+    // of writing out of bounds.
+    {
+        const unsigned long long cend = last ? tot : cout_next;
+        const unsigned long long sbytes = ((unsigned long long)n + 7) / 8 + 1;
+        if (n > (uint32_t)kChunkWordsCap * 32u || cout > cend || cend > tot ||
+            (unsigned long long)hdr + cout + 2 * sbytes > out_stride) {
+            if (lane == 0) {
+                out_len[frame] = 0;
+                raise_status(status, 16);
+            }
+            return;
+        }
+    }
+    const ChunkSpan sp = chunk_span(g, c);
+    uint8_t* const base = out + (size_t)frame * out_stride + hdr;
+    if (lane == 0) {
+        if (last && !g.more_after) {  // EOI (encoder.rs:131) and the file size
+            base[tot] = 0xFF;
+            base[tot + 1] = 0xD9;
+            out_len[frame] = (uint32_t)(end + 2);
+        } else if (sp.seg_last && g.restart_interval > 0) {  // RSTm closing restart segment m (extension; not stuffed)
+            const unsigned long long at = (last ? tot : cout_next) - 2;
+            base[at] = 0xFF;
+            base[at + 1] = (uint8_t)(0xD0 + ((g.seg_base + sp.seg) & 7));
+            if (last) out_len[frame] = (uint32_t)end;  // a stripe that more stripes follow
+        } else if (last) {
+            out_len[frame] = (uint32_t)end;  // a joined stripe that more stripes follow
+        }
+    }
+    const unsigned long long e = b0 + n;
+    const unsigned long long kbeg = (b0 + 7) >> 3, kend = (e + 7) >> 3;
+    if (kend <= kbeg) return;  // a tail chunk inside the previous chunk's last byte
+    const uint32_t nbytes = (uint32_t)(kend - kbeg);  // (n <= 32 kChunkWordsCap)
+    // the chunk's last byte, when shared with the next chunk or the padding
+    const bool shared_tail = (e & 7) != 0;
+    uint32_t tail = 0;
+    if (shared_tail) {
+        const bool jt = joined_tail(g, c);
+        const bool has_next = !sp.seg_last || jt;
+        tail = boundary_byte((int)(e & 7), edge & 0xFFFFu, has_next,
+                             jt ? (uint32_t)g.next_bits : (has_next ? n_next : 0u),
+                             jt ? g.next16 : (has_next ? edge_next >> 16 : 0u));
+    }
+    const int sh = (int)(8 * kbeg - b0);  // the first owned byte starts this many bits into the chunk (< 8)
+    uint8_t* o = base + cout;
+    // one pass: bytes [pos, pos + kStuffWavePass) of the chunk from this lane's slot words wv
+    auto pass = [&](uint32_t pos, const uint32_t (&wv)[5]) {
+        // the pass is staged at o's alignment (sOut[delta + i] = output byte i), so
+        // it leaves LDS in aligned 16-byte stores
+        const uint32_t delta = (uint32_t)(reinterpret_cast<uintptr_t>(o) & 15u);
+        const uint32_t kb = pos + 16u * (uint32_t)lane;  // first of my 16 bytes (chunk-relative)
+        const int nvalid = kb < nbytes ? (int)min(16u, nbytes - kb) : 0;
+        uint32_t x[4] = {0u, 0u, 0u, 0u};    // my 16 bytes, MSB first
+        uint32_t ffm[4] = {0u, 0u, 0u, 0u};  // bit 7 of every valid byte of x that is 0xFF
+        uint32_t cnt = 0;
+        if (nvalid) cnt = stuff_piece(wv, sh, nvalid, shared_tail && nbytes - 1 - kb < 16, (int)(nbytes - 1 - kb), tail, x, ffm);
+        const uint32_t incl = wave_incl_scan_full_u32(cnt);
+        const uint32_t ffs = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        // staged in LDS, then stored with consecutive lanes on consecutive bytes (coalesced)
+        if (nvalid) stuff_stage(sOut, delta + (uint32_t)lane * 16u + (incl - cnt), x, ffm, cnt);
+        wave_lds_sync();
+        const uint32_t len = min(nbytes - pos, (uint32_t)kStuffWavePass) + ffs;
+        const uint32_t send = delta + len;  // staged bytes [delta, send)
+        uint8_t* const oa = o - delta;      // 16-byte aligned
+        for (uint32_t sb = 16u * (uint32_t)lane; sb + 16u <= send; sb += 16u * 64u) {
+            if (sb >= delta) *reinterpret_cast<uint4*>(oa + sb) = *reinterpret_cast<const uint4*>(sOut + sb);
+        }
+        // The pass's first and last 16-byte pieces where they are not whole: only the
+        // pass's own bytes, one per lane.  Lanes 0..15 take the first piece,
+        // [delta, 16) cut at send; lanes 16..31 the last one from its 16-byte boundary
+        // sbt to send, unless it is the first.
+        if (lane < 32) {
+            const uint32_t sbt = send & ~15u;
+            const uint32_t i = lane < 16 ? (uint32_t)lane : sbt + (uint32_t)lane - 16u;
+            const bool mine = lane < 16 ? i >= delta && (delta > 0u || send < 16u) : sbt > 0u;
+            if (mine && i < send) oa[i] = sOut[i];
+        }
+        o += len;
+        wave_lds_sync();  // sOut reuse
+    };
+#pragma unroll
+    for (int k = 0; k < kStuffPre; ++k) {
+        if ((uint32_t)(kStuffWavePass * k) >= nbytes) return;  // uniform
+        pass((uint32_t)(kStuffWavePass * k), wpre[k]);
+    }
+    for (uint32_t pos = kStuffPre * kStuffWavePass; pos < nbytes; pos += kStuffWavePass) {  // uniform
+        uint32_t wv[5] = {0u, 0u, 0u, 0u, 0u};
+        if (pos + 16u * (uint32_t)lane < nbytes) {
+            const uint32_t* w = slot + (pos >> 2) + 4 * lane;
+            const uint4 q = *reinterpret_cast<const uint4*>(w);
+            wv[0] = q.x, wv[1] = q.y, wv[2] = q.z, wv[3] = q.w;
+            wv[4] = w[4];
+        }
+        pass(pos, wv);
+    }
+}
+#else
+// Study build: one workgroup per chunk, passes of 4096 bytes (16 per thread).
+constexpr int kStuffPass = 4096;
 __global__ __launch_bounds__(256, 8) void k_stuffwrite(const uint32_t* __restrict__ stage,
                                                     const uint32_t* __restrict__ chunk_bits,
                                                     const uint32_t* __restrict__ chunk_edge,
@@ -1225,25 +1462,11 @@ __global__ __launch_bounds__(256, 8) void k_stuffwrite(const uint32_t* __restric
         if (nvalid) {
             const unsigned long long p = off + 8 * kb;  // bit position in the chunk stream (off < 8)
             const size_t wi = (size_t)(p >> 5);
-            const int sh = (int)(p & 31);
             uint32_t wv[5];
 #pragma unroll
             for (int i = 0; i < 5; ++i) wv[i] = pos ? slot[wi + i] : wv0[i];  // (pass 0: wi = 4 tid)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) x[i] = sh ? (wv[i] << sh) | (wv[i + 1] >> (32 - sh)) : wv[i];
-            if (shared_tail && nbytes - 1 - kb < 16) {  // the shared / padded last byte
-                const int j = (int)(nbytes - 1 - kb), sft = 24 - 8 * (j & 3);
-                x[j >> 2] = (x[j >> 2] & ~(0xFFu << sft)) | (tail << sft);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {  // 0xFF bytes among the valid ones
-                const int nv = min(max(nvalid - 4 * i, 0), 4);
-                const uint32_t vmask = nv ? 0x80808080u & (0xFFFFFFFFu << (32 - 8 * nv)) : 0u;
-                const uint32_t t = ~x[i];
-                const uint32_t nonzero = (((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t) & 0x80808080u;
-                ffm[i] = ~nonzero & vmask;
-                cnt += (uint32_t)__popc(ffm[i]);
-            }
+            cnt = stuff_piece(wv, (int)(p & 31), nvalid, shared_tail && nbytes - 1 - kb < 16, (int)(nbytes - 1 - kb), tail,
+                              x, ffm);
         }
         const uint32_t incl = wave_incl_scan_full_u32(cnt);
         if (lane == 63) sWave[wave] = incl;
@@ -1260,31 +1483,7 @@ __global__ __launch_bounds__(256, 8) void k_stuffwrite(const uint32_t* __restric
         // the pieces that hold a 0xFF (about 6 % at 4K q90) then enter one region
         // for their 0x00 bytes, a loop over the set bits (STUDIES section H).
         if (nvalid) {
-            const uint32_t dst = delta + (uint32_t)tid * 16u + pre;
-            uint32_t a = dst;  // where byte 4 i goes
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const uint32_t w = x[i], f = ffm[i];
-                sOut[a + 4 * i] = (uint8_t)(w >> 24);
-                sOut[a + (uint32_t)__popc(f & 0x80000000u) + 4 * i + 1] = (uint8_t)(w >> 16);
-                sOut[a + (uint32_t)__popc(f & 0x80800000u) + 4 * i + 2] = (uint8_t)(w >> 8);
-                sOut[a + (uint32_t)__popc(f & 0x80808000u) + 4 * i + 3] = (uint8_t)w;
-                a += (uint32_t)__popc(f);
-            }
-            if (cnt) {
-                // bit j of m: byte j is 0xFF (the four flags of a word, at bits 24, 16, 8
-                // and 0 once shifted, gathered by one multiplication without carries)
-                uint32_t m = 0;
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    m |= ((((ffm[i] >> 7) * 0x08040201u) >> 24) & 0xFu) << (4 * i);
-                uint32_t z = dst + 1;  // the 0x00 of the first 0xFF byte, were it byte 0
-                while (m) {
-                    sOut[z + (uint32_t)__builtin_ctz(m)] = 0x00;
-                    ++z;
-                    m &= m - 1u;
-                }
-            }
+            stuff_stage(sOut, delta + (uint32_t)tid * 16u + pre, x, ffm, cnt);
         }
         __syncthreads();
         const unsigned long long in_pass = nbytes - pos < (unsigned long long)kStuffPass ? nbytes - pos : kStuffPass;
@@ -1308,6 +1507,7 @@ __global__ __launch_bounds__(256, 8) void k_stuffwrite(const uint32_t* __restric
         __syncthreads();  // sWave / sOut reuse
     }
 }
+#endif
 
 // --------------------------------------------------------------------- launchers
 bool offsets_fusable(const Geom& g) { return g.nch <= kFusedOffsetsMaxChunks; }
@@ -1345,7 +1545,8 @@ hipError_t launch_offsets(int n_frames, const Geom& g, const Work& w, hipStream_
 
 hipError_t launch_stuffwrite(int n_frames, const Geom& g, const Work& w, uint8_t* out, size_t out_stride,
                              uint32_t* out_len, hipStream_t st) {
-    hipLaunchKernelGGL(k_stuffwrite, dim3(g.nch, n_frames), dim3(256), 0, st, (const uint32_t*)w.stage,
+    const int per_wg = DMMT_STUFF_WAVE_CHUNK ? 4 : 1;  // chunks per workgroup
+    hipLaunchKernelGGL(k_stuffwrite, dim3((g.nch + per_wg - 1) / per_wg, n_frames), dim3(256), 0, st, (const uint32_t*)w.stage,
                        (const uint32_t*)w.chunk_bits, (const uint32_t*)w.chunk_edge,
                        (const unsigned long long*)w.chunk_bit0, (const unsigned long long*)w.chunk_out,
                        (const unsigned long long*)w.total_out, (const uint32_t*)w.hdr_len, g, out, out_stride,

@@ -142,10 +142,12 @@ __device__ __forceinline__ void front_column_pass(const float* sT, const float* 
     const int nvalid = min(G::TM, g.mcux - mx0) * G::BPM;
     const long long e0 = (long long)frame * g.bpf + ((long long)my * g.mcux + mx0) * G::BPM;
     int16_t* const cbase = coef + e0 * 64;  // (uniform: the stores take a 32-bit lane offset)
+    constexpr bool FOLD = NARROW && DMMT_NARROW_FOLD;
 #pragma unroll
     for (int jj = 0; jj < G::JPT; ++jj) {
         const int blk = (tid + 256 * jj) >> 3;
         int x[8];
+        float mag = 0.0f;  // FOLD: the largest magnitude among the column's hi rows
         {
             const int qt = G::NQT == 1 || blk < G::NYB ? 0 : 64;
             const float* q = sQ + qt + col;
@@ -157,6 +159,9 @@ __device__ __forceinline__ void front_column_pass(const float* sT, const float* 
             if constexpr (F32) {
                 arai8(v);
                 quantize_col8(v, q, rq, x);
+            } else if constexpr (FOLD) {
+                arai8_unscaled(v);
+                quantize_col8_scaled_fold(v, q, rq, nan_possible, x, [&](float m, int r, float n) { return coef_hi_mag_row(m, r, n, col); }, mag);
             } else {
                 arai8_unscaled(v);
                 quantize_col8_scaled(v, q, rq, nan_possible, x);
@@ -165,7 +170,7 @@ __device__ __forceinline__ void front_column_pass(const float* sT, const float* 
         const int el = G::NCOMP == 1 ? blk : G::emit_index(blk);
         const bool valid = el < nvalid;  // (uniform over the block's 8 lanes)
         if constexpr (NARROW) {
-            coef_store_column_narrow(x, col, el, valid, cbase, coef_lo + e0 * 8, coef_hi + e0 * 64);
+            coef_store_column_narrow<FOLD>(x, mag > kCoefHiMagMax, col, el, valid, cbase, coef_lo + e0 * 8, coef_hi + e0 * 64);
         } else if (valid) {
             uint32_t pk[4];  // the low halves of two coefficients per word (one v_perm_b32)
 #pragma unroll

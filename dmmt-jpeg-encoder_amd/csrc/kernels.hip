@@ -1212,13 +1212,6 @@ constexpr int kTailLevels = 15;
 constexpr int kTailBase[4] = {0, 208, 3536, 3744};
 static_assert(kTailBase[3] + 3328 == kTailLdsBytes, "tables_tail's LDS regions");
 
-// The tail's phases pass data between the lanes of ONE wave through LDS: a wave's
-// LDS operations complete in order, so no s_barrier -- only no code motion across.
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // Levels 1-14 of the package-merge over n leaves F (ascending) in 64 * EPL element
 // merges (n <= 32 * EPL): slot-major, the leaves ascending in the lower half
 // (static), the packages DESCENDING in the upper (element S/2 + m holds package
