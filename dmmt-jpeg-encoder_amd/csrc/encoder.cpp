@@ -454,12 +454,15 @@ int enqueue_back_half(dmmt_ctx* c, const Geom& g, int nf, const Work& w, int bit
 
 int enqueue_direct(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, int nf, const Geom& g,
                    const Work& w, int bits, uint8_t* out, size_t out_stride, uint32_t* out_len, hipStream_t st,
-                   const Surface* sf = nullptr, const YccFrames* yf = nullptr, const GrayPlane* gp = nullptr) {
+                   const Surface* sf = nullptr, const YccFrames* yf = nullptr, const GrayPlane* gp = nullptr,
+                   const YccLevels* lv = nullptr) {
     {
         StageTimer t(c, ST_FRONT, st);
         const int cap = c->nlanes > 1 ? DMMT_FRONT_PER_CU_LANES : 0;
         if (gp)  // a one-channel plane: d_rgb is the plane
             HIP_TRY(launch_front_gray(*gp, frame_stride, sb, nf, g, w, st, cap));
+        else if (yf && lv)  // YCbCr planes of other levels than uint8 full range
+            HIP_TRY(launch_front_ycc_levels(*yf, *lv, frame_stride, nf, g, w, st, cap));
         else if (yf)  // YCbCr planes (uint8): d_rgb is the luma plane
             HIP_TRY(launch_front_ycc(*yf, frame_stride, nf, g, w, st, cap));
         else if (sf)  // a surface: d_rgb is its first plane
@@ -482,7 +485,7 @@ void destroy_graphs(dmmt_ctx* c) {
 int enqueue_encode(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, int nf, const Geom& g,
                    const dmmt_options* opt, uint8_t* out, size_t out_stride, uint32_t* out_len, hipStream_t st,
                    int lane = 0, bool async = false, int* status = nullptr, const Surface* sf = nullptr,
-                   const YccFrames* yf = nullptr, const GrayPlane* gray = nullptr) {
+                   const YccFrames* yf = nullptr, const GrayPlane* gray = nullptr, const YccLevels* lv = nullptr) {
     Work w;
     int rc;
     if ((rc = prepare(c, g, nf, opt, sb, st, &w, lane, async, status, true))) return rc;
@@ -498,7 +501,7 @@ int enqueue_encode(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, 
     // (a per-file status area -- dmmt_convert_ppm_device_batch -- would put a new
     // pointer into every file's graph key: that path launches directly)
     if (!c->use_graphs || c->profile || status)
-        return enqueue_direct(c, d_rgb, frame_stride, sb, nf, g, w, bits, out, out_stride, out_len, st, sf, yf, gp);
+        return enqueue_direct(c, d_rgb, frame_stride, sb, nf, g, w, bits, out, out_stride, out_len, st, sf, yf, gp, lv);
     std::vector<uint64_t> key = {(uint64_t)(uintptr_t)d_rgb, (uint64_t)frame_stride, (uint64_t)sb, (uint64_t)nf,
                                  (uint64_t)g.width, (uint64_t)g.height, (uint64_t)g.hr, (uint64_t)g.vr,
                                  (uint64_t)g.maxval, (uint64_t)g.restart_interval, (uint64_t)bits,
@@ -511,6 +514,9 @@ int enqueue_encode(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, 
     if (yf)  // YCbCr planes: two descriptions may share their luma pointer
         key.insert(key.end(), {(uint64_t)yf->format + 16, (uint64_t)yf->luma_pitch, (uint64_t)yf->chroma_pitch,
                                (uint64_t)(uintptr_t)yf->plane[1], (uint64_t)(uintptr_t)yf->plane[2]});
+    if (lv)  // the same planes and pitches read as other levels are another front kernel or other arguments
+        key.insert(key.end(), {(uint64_t)lv->range + 64, (uint64_t)lv->bit_depth, (uint64_t)lv->sample_bytes,
+                               (uint64_t)lv->shift});
     // a gray call and a 4:4:4 colour call of the same size share every field above: the
     // component count, the transfer (through the table's contents the graph reads, and the
     // table's address), the plane and its pitch
@@ -527,7 +533,7 @@ int enqueue_encode(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, 
     if (!hit) {
         hipGraph_t graph = nullptr;
         HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        rc = enqueue_direct(c, d_rgb, frame_stride, sb, nf, g, w, bits, out, out_stride, out_len, st, sf, yf, gp);
+        rc = enqueue_direct(c, d_rgb, frame_stride, sb, nf, g, w, bits, out, out_stride, out_len, st, sf, yf, gp, lv);
         hipError_t e = hipStreamEndCapture(st, &graph);
         if (rc) {
             if (graph) (void)hipGraphDestroy(graph);
@@ -789,11 +795,12 @@ extern "C" size_t dmmt_max_jpeg_bytes(uint16_t width, uint16_t height, int32_t s
 }
 
 // dmmt_encode_device, dmmt_encode_device_surfaces (sf: the surface, whose first
-// plane is f->d_rgb) and dmmt_encode_device_ycc (yf: the planes, f->d_rgb the luma
-// plane) after their own argument checks
+// plane is f->d_rgb) and dmmt_encode_device_ycc[_levels] (yf: the planes, f->d_rgb
+// the luma plane; lv: their levels unless uint8 full range) after their own
+// argument checks
 static int encode_device_frames(dmmt_ctx* c, const dmmt_device_frames* f, const dmmt_options* opt, void* stream,
                                 const Geom& g, const Surface* sf, const YccFrames* yf = nullptr,
-                                const GrayPlane* gp = nullptr) {
+                                const GrayPlane* gp = nullptr, const YccLevels* lv = nullptr) {
     int rc;
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = set_device(c))) return rc;
@@ -804,7 +811,7 @@ static int encode_device_frames(dmmt_ctx* c, const dmmt_device_frames* f, const 
         HIP_TRY(hipEventRecord(c->ev_lane0, c->stream));
         HIP_TRY(hipStreamWaitEvent(st, c->ev_lane0, 0));
         rc = enqueue_encode(c, f->d_rgb, f->frame_stride, f->sample_bytes, f->n_frames, g, opt, f->d_out,
-                            f->out_stride, f->d_out_len, st, 0, true, nullptr, sf, yf, gp);
+                            f->out_stride, f->d_out_len, st, 0, true, nullptr, sf, yf, gp, lv);
         HIP_TRY(hipEventRecord(c->ev_caller, st));
         HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_caller, 0));
         return rc;
@@ -812,7 +819,7 @@ static int encode_device_frames(dmmt_ctx* c, const dmmt_device_frames* f, const 
     int lane = 0;  // pipelined: the next lane's workspace and stream
     if (c->nlanes > 1) lane = (int)(c->next_lane++ % (unsigned)c->nlanes);
     return enqueue_encode(c, f->d_rgb, f->frame_stride, f->sample_bytes, f->n_frames, g, opt, f->d_out, f->out_stride,
-                          f->d_out_len, c->lanes[lane]->stream, lane, true, nullptr, sf, yf, gp);
+                          f->d_out_len, c->lanes[lane]->stream, lane, true, nullptr, sf, yf, gp, lv);
 }
 
 extern "C" int dmmt_encode_device(dmmt_ctx* c, const dmmt_device_frames* f, const dmmt_options* opt, void* stream) {
@@ -875,13 +882,27 @@ static int ycc_rates(int sub, int* hr, int* vr) {
     return 1;
 }
 
-extern "C" size_t dmmt_ycc_plane_span(const dmmt_device_ycc* y, int plane) {
-    int hr, vr;
-    if (!y || !y->width || !y->height || !ycc_rates(y->chroma_sampling, &hr, &vr)) return 0;
-    return ycc_plane_span(y->format, plane, y->width, y->height, hr, vr, y->luma_pitch, y->chroma_pitch);
+// dmmt_ycc_levels as the kernels' YccLevels; NULL: uint8 full range
+static YccLevels ycc_levels_of(const dmmt_ycc_levels* l) {
+    if (!l) return YccLevels{YCC_RANGE_FULL, 8, 1, 0};
+    return YccLevels{l->range, l->bit_depth, l->sample_bytes, l->shift};
 }
 
-extern "C" int dmmt_encode_device_ycc(dmmt_ctx* c, const dmmt_device_ycc* y, const dmmt_options* opt, void* stream) {
+extern "C" size_t dmmt_ycc_plane_span_levels(const dmmt_device_ycc* y, const dmmt_ycc_levels* levels, int plane) {
+    int hr, vr;
+    if (!y || !y->width || !y->height || !ycc_rates(y->chroma_sampling, &hr, &vr)) return 0;
+    const YccLevels lv = ycc_levels_of(levels);
+    if (!ycc_levels_valid(lv)) return 0;
+    return ycc_plane_span_levels(y->format, plane, y->width, y->height, hr, vr, y->luma_pitch, y->chroma_pitch,
+                                 lv.sample_bytes);
+}
+
+extern "C" size_t dmmt_ycc_plane_span(const dmmt_device_ycc* y, int plane) {
+    return dmmt_ycc_plane_span_levels(y, nullptr, plane);
+}
+
+extern "C" int dmmt_encode_device_ycc_levels(dmmt_ctx* c, const dmmt_device_ycc* y, const dmmt_ycc_levels* levels,
+                                             const dmmt_options* opt, void* stream) {
     c = primary(c);
     if (!c || !y) return DMMT_E_INVALID_ARGUMENT;
     int rc;
@@ -889,27 +910,39 @@ extern "C" int dmmt_encode_device_ycc(dmmt_ctx* c, const dmmt_device_ycc* y, con
     if (y->n_frames <= 0 || !y->d_out || !y->d_out_len) return DMMT_E_INVALID_ARGUMENT;
     if (y->format < DMMT_YCC_PLANAR || y->format > DMMT_YCC_NV_VU) return DMMT_E_INVALID_ARGUMENT;
     if (y->chroma_sampling != opt->subsampling) return DMMT_E_INVALID_ARGUMENT;  // no conversion between samplings
+    const YccLevels lv = ycc_levels_of(levels);
+    if (!ycc_levels_valid(lv)) return DMMT_E_INVALID_ARGUMENT;
+    const size_t sb = (size_t)lv.sample_bytes;
     const int nplanes = y->format == DMMT_YCC_PLANAR ? 3 : 2;
     for (int p = 0; p < nplanes; ++p)
-        if (!y->d_plane[p]) return DMMT_E_INVALID_ARGUMENT;
+        if (!y->d_plane[p] || (uintptr_t)y->d_plane[p] % sb) return DMMT_E_INVALID_ARGUMENT;
     Geom g;
     if ((rc = make_checked_geom(y->width, y->height, opt->subsampling, 255, opt->restart_interval, &g))) return rc;
-    const size_t chroma_row = (size_t)((g.width + g.hr - 1) / g.hr) * (y->format == DMMT_YCC_PLANAR ? 1 : 2);
-    if (y->luma_pitch < (size_t)g.width || y->luma_pitch > DMMT_MAX_ROW_PITCH || y->chroma_pitch < chroma_row ||
+    const size_t chroma_row = (size_t)((g.width + g.hr - 1) / g.hr) * (y->format == DMMT_YCC_PLANAR ? 1 : 2) * sb;
+    if (y->luma_pitch < (size_t)g.width * sb || y->luma_pitch > DMMT_MAX_ROW_PITCH || y->chroma_pitch < chroma_row ||
         y->chroma_pitch > DMMT_MAX_ROW_PITCH)
         return DMMT_E_INVALID_ARGUMENT;
+    if (y->luma_pitch % sb || y->chroma_pitch % sb || y->frame_stride % sb) return DMMT_E_INVALID_ARGUMENT;
     if (y->out_stride < max_jpeg_bytes(g)) return DMMT_E_CAPACITY;
     YccFrames yf{};
     for (int p = 0; p < nplanes; ++p) yf.plane[p] = y->d_plane[p];
     yf.luma_pitch = y->luma_pitch, yf.chroma_pitch = y->chroma_pitch;
     yf.format = y->format;
+    // uint8 full range is k_front_ycc's contract: the same kernel, the same graph key
+    const bool plain = lv.range == YCC_RANGE_FULL && lv.sample_bytes == 1;
+    // (the context's view of the samples stays "8-bit, maxval 255" whatever the levels:
+    // the normalisation table is not read, and the block form is chosen as for uint8)
     dmmt_device_frames f{};
     f.d_rgb = y->d_plane[0];
     f.frame_stride = y->frame_stride;
     f.n_frames = y->n_frames;
     f.width = y->width, f.height = y->height, f.maxval = 255, f.sample_bytes = 1;
     f.d_out = y->d_out, f.out_stride = y->out_stride, f.d_out_len = y->d_out_len;
-    return encode_device_frames(c, &f, opt, stream, g, nullptr, &yf);
+    return encode_device_frames(c, &f, opt, stream, g, nullptr, &yf, nullptr, plain ? nullptr : &lv);
+}
+
+extern "C" int dmmt_encode_device_ycc(dmmt_ctx* c, const dmmt_device_ycc* y, const dmmt_options* opt, void* stream) {
+    return dmmt_encode_device_ycc_levels(c, y, nullptr, opt, stream);
 }
 
 // the checks dmmt_encode_device_gray and dmmt_jpeg_encode_gray share

@@ -205,11 +205,7 @@ static int ycc_chroma_width(int width, int hr) { return (width + hr - 1) / hr; }
 
 size_t ycc_plane_span(int format, int plane, int width, int height, int hr, int vr, size_t luma_pitch,
                       size_t chroma_pitch) {
-    if (format < YCC_PLANAR || format > YCC_NV_VU || width <= 0 || height <= 0) return 0;
-    if (plane == 0) return (size_t)(height - 1) * luma_pitch + (size_t)width;
-    if (plane != 1 && !(plane == 2 && format == YCC_PLANAR)) return 0;
-    const size_t cw = (size_t)ycc_chroma_width(width, hr), ch = (size_t)((height + vr - 1) / vr);
-    return (ch - 1) * chroma_pitch + cw * (format == YCC_PLANAR ? 1 : 2);
+    return ycc_plane_span_levels(format, plane, width, height, hr, vr, luma_pitch, chroma_pitch, 1);  // uint8
 }
 
 hipError_t launch_front_ycc(const YccFrames& yf, size_t frame_stride_bytes, int n_frames, const Geom& g, const Work& w,

@@ -72,6 +72,28 @@ size_t ycc_plane_span(int format, int plane, int width, int height, int hr, int 
 hipError_t launch_front_ycc(const YccFrames& yf, size_t frame_stride_bytes, int n_frames, const Geom& g, const Work& w,
                             hipStream_t st, int per_cu_cap = 0);
 
+// The sample levels of YCbCr frames (dmmt_ycc_levels): range as dmmt_ycc_range
+enum { YCC_RANGE_FULL = 0, YCC_RANGE_LIMITED = 1 };
+struct YccLevels {
+    int range, bit_depth, sample_bytes, shift;
+};
+// code v -> the DCT's input: luma min(max((v - off_y) * k_y, 0), 255) - 128, chroma
+// min(max((v - off_c) * k_c, -128), 127), in f32, each operation rounded once
+struct YccTransfer {
+    float off_y, k_y, off_c, k_c;
+};
+// a description the levels kernels take: uint8 with 8 bits, uint16 with 8..16 bits
+// and shift <= 16 - bits
+bool ycc_levels_valid(const YccLevels& lv);
+YccTransfer ycc_levels_transfer(const YccLevels& lv);  // (host; lv valid)
+// ycc_plane_span with sample_bytes bytes per sample (0: not 1 or 2)
+size_t ycc_plane_span_levels(int format, int plane, int width, int height, int hr, int vr, size_t luma_pitch,
+                             size_t chroma_pitch, int sample_bytes);
+// k_front_ycc_lv (front_ycc_levels.hip): planes of any valid levels -> w.coef, as
+// launch_front_ycc; a code above 2^bits - 1 raises status bit 1
+hipError_t launch_front_ycc_levels(const YccFrames& yf, const YccLevels& lv, size_t frame_stride_bytes, int n_frames,
+                                   const Geom& g, const Work& w, hipStream_t st, int per_cu_cap = 0);
+
 // A one-channel plane (dmmt_device_gray): transfer as dmmt_gray_transfer
 enum { GRAY_AS_RGB = 0, GRAY_Y_FULL_RANGE = 1 };
 struct GrayPlane {

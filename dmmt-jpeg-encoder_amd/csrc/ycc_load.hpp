@@ -17,6 +17,12 @@
 // (0 - 128 = -128, black) and 0x80 for chroma (128 - 128 = 0, no colour), the
 // reference's black padding (padder.rs:12-42) in YCbCr.  Phase A needs no bounds
 // checks.
+//
+// SB: bytes per sample, 1 (uint8) or 2 (uint16, front_ycc_levels.hip; every pitch,
+// plane address and so every offset and misalignment even).  Every byte count above
+// scales with it: a luma tile row is 256 * SB bytes, a chroma position SB or 2 * SB
+// bytes.  The pad samples are then the caller's (luma_fill, chroma_fill: the code
+// that transfers to black, in every sample of a 32-bit word).
 #pragma once
 #include <stdint.h>
 
@@ -35,16 +41,17 @@ struct YccDesc {
 // Tile geometry.  NV: the chroma plane holds pairs.  Chunk q of a tile: the luma
 // chunks first (tile row q / LRC, chunk q % LRC of it), then the chroma tile rows
 // (plane-major: all 8 rows of Cb, then of Cr), CRC chunks each.
-template <int HR_, int VR_, bool NV_>
+template <int HR_, int VR_, bool NV_, int SB_ = 1>
 struct YccTile {
-    static constexpr int HR = HR_, VR = VR_;
+    static_assert(SB_ == 1 || SB_ == 2, "uint8 or uint16 samples");
+    static constexpr int HR = HR_, VR = VR_, SB = SB_;
     static constexpr bool NV = NV_;
     static constexpr int ROWS = 8 * VR;               // luma tile rows
-    static constexpr int LRB = 256;                   // bytes of a luma tile row
+    static constexpr int LRB = 256 * SB;              // bytes of a luma tile row
     static constexpr int LRC = LRB / 16 + 1;          // its chunks at any misalignment
     static constexpr int LRS = LRC * 16;              // its stride in LDS
     static constexpr int CPX = 256 / HR;              // chroma positions of a tile row
-    static constexpr int CBPP = NV ? 2 : 1;           // bytes per chroma position of a plane
+    static constexpr int CBPP = (NV ? 2 : 1) * SB;    // bytes per chroma position of a plane
     static constexpr int CRB = CPX * CBPP, CRC = CRB / 16 + 1, CRS = CRC * 16;
     static constexpr int NCPL = NV ? 1 : 2;           // chroma planes
     static constexpr int NLC = ROWS * LRC;            // luma chunks
@@ -83,8 +90,8 @@ template <class T>
 DMMT_SURF_FN bool ycc_tile_interior(const YccDesc& d, int x0, int y0) {
     if (x0 + 256 > d.width || y0 + T::ROWS > d.height) return false;
     const int cx0 = x0 / T::HR, cy0 = y0 / T::VR;
-    return surf_interior(surf_row_start(d.luma_pitch, 1, x0, y0), surf_row_start(d.luma_pitch, 1, x0, y0 + T::ROWS - 1),
-                         T::LRB, d.luma_span) &&
+    return surf_interior(surf_row_start(d.luma_pitch, T::SB, x0, y0),
+                         surf_row_start(d.luma_pitch, T::SB, x0, y0 + T::ROWS - 1), T::LRB, d.luma_span) &&
            surf_interior(surf_row_start(d.chroma_pitch, T::CBPP, cx0, cy0),
                          surf_row_start(d.chroma_pitch, T::CBPP, cx0, cy0 + 7), T::CRB, d.chroma_span);
 }
@@ -93,15 +100,16 @@ DMMT_SURF_FN bool ycc_tile_interior(const YccDesc& d, int x0, int y0) {
 //   plane(p) -> Mem     plane p of the frame (0: Y, 1: Cb or the pairs, 2: Cr), with
 //                       load16 / load1 as surf_load_chunk and
 //   uint32_t base_lo()  the low bits of the plane's address
+// luma_fill, chroma_fill: the pad samples, as 32-bit words
 template <class T, class Mems>
 DMMT_SURF_FN void ycc_tile_chunk(const Mems& ms, const YccDesc& d, int x0, int y0, bool interior, int q,
-                                 uint32_t (&w)[4]) {
+                                 uint32_t (&w)[4], uint32_t luma_fill = 0u, uint32_t chroma_fill = 0x80808080u) {
     const bool luma = q < T::NLC;
     const int qc = luma ? q : q - T::NLC;
     const int rc = luma ? T::LRC : T::CRC;
     const int tr = qc / rc, j = qc - tr * rc;
     const int p = luma ? 0 : 1 + (tr >> 3);
-    const int bpp = luma ? 1 : T::CBPP;
+    const int bpp = luma ? T::SB : T::CBPP;
     const int px0 = luma ? x0 : x0 / T::HR;
     const int py = luma ? y0 + tr : y0 / T::VR + (tr & 7);
     const long long pitch = luma ? d.luma_pitch : d.chroma_pitch;
@@ -111,7 +119,7 @@ DMMT_SURF_FN void ycc_tile_chunk(const Mems& ms, const YccDesc& d, int x0, int y
         m.load16(surf_interior_chunk(m.base_lo(), start, j), w);
         return;
     }
-    const uint32_t fill = luma ? 0u : 0x80808080u;
+    const uint32_t fill = luma ? luma_fill : chroma_fill;
     w[0] = w[1] = w[2] = w[3] = fill;
     if (py >= (luma ? d.height : d.ch)) return;  // a row below the plane's last: the pad sample
     const int mis = surf_misalign32(m.base_lo(), (uint32_t)pitch, bpp, px0, py);

@@ -91,6 +91,9 @@ def lib():
     L.dmmt_encode_device_ycc.argtypes = [vp, P(DmmtDeviceYcc), P(DmmtOptions), vp]
     L.dmmt_ycc_plane_span.argtypes = [P(DmmtDeviceYcc), ctypes.c_int]
     L.dmmt_ycc_plane_span.restype = sz
+    L.dmmt_encode_device_ycc_levels.argtypes = [vp, P(DmmtDeviceYcc), P(DmmtYccLevels), P(DmmtOptions), vp]
+    L.dmmt_ycc_plane_span_levels.argtypes = [P(DmmtDeviceYcc), P(DmmtYccLevels), ctypes.c_int]
+    L.dmmt_ycc_plane_span_levels.restype = sz
     L.dmmt_encode_device_gray.argtypes = [vp, P(DmmtDeviceGray), P(DmmtOptions), vp]
     L.dmmt_gray_span.argtypes = [P(DmmtDeviceGray)]
     L.dmmt_gray_span.restype = sz
@@ -223,6 +226,26 @@ class YccFormat(enum.IntEnum):
 def ycc_plane_span(y: DmmtDeviceYcc, plane: int) -> int:
     """dmmt_ycc_plane_span: the bytes of a plane the encoder may read, per frame"""
     return int(lib().dmmt_ycc_plane_span(ctypes.byref(y), int(plane)))
+
+
+class DmmtYccLevels(ctypes.Structure):
+    """dmmt_ycc_levels: the sample levels of YCbCr planes.  P010: (LIMITED, 10, 2, 6);
+    I010 / yuv420p10le: (.., 10, 2, 0); 8-bit limited NV12: (LIMITED, 8, 1, 0)"""
+    _fields_ = [("range", ctypes.c_int32), ("bit_depth", ctypes.c_int32), ("sample_bytes", ctypes.c_int32),
+                ("shift", ctypes.c_int32)]
+
+
+class YccRange(enum.IntEnum):
+    """dmmt_ycc_range: what the codes of a YCbCr sample mean"""
+    FULL = 0     # JFIF: Y, Cb, Cr in 0 .. 2^B - 1, chroma centred on 2^(B-1)
+    LIMITED = 1  # video: Y 16 m .. 235 m, chroma 16 m .. 240 m, m = 2^(B-8)
+
+
+def ycc_plane_span_levels(y: DmmtDeviceYcc, levels: DmmtYccLevels | None, plane: int) -> int:
+    """dmmt_ycc_plane_span_levels: the bytes of a plane the encoder may read, per frame,
+    for samples of these levels (None: uint8 full range)"""
+    return int(lib().dmmt_ycc_plane_span_levels(ctypes.byref(y), ctypes.byref(levels) if levels is not None else None,
+                                                int(plane)))
 
 
 class DmmtDeviceGray(ctypes.Structure):
@@ -628,20 +651,29 @@ class Encoder:
     def encode_device_ycc(self, d_planes, fmt: int, luma_pitch: int, chroma_pitch: int, n_frames: int, width: int,
                           height: int, options: JpegTransformationOptions, d_out: int, out_stride: int,
                           d_out_len: int, frame_stride: int = 0, stream: int | None = None,
-                          opt_c: DmmtOptions | None = None):
+                          opt_c: DmmtOptions | None = None, levels: DmmtYccLevels | None = None):
         """dmmt_encode_device_ycc: uint8 full-range YCbCr planes in HBM, subsampled as
-        options.chroma_subsampling_preset says; enqueued, see synchronize()"""
+        options.chroma_subsampling_preset says; enqueued, see synchronize().  levels:
+        dmmt_encode_device_ycc_levels -- limited range, 8 to 16 bits in uint16 samples
+        (pitches and frame_stride stay in bytes)"""
         opt = opt_c if opt_c is not None else options.to_c()
         y = self.ycc(d_planes, fmt, luma_pitch, chroma_pitch, n_frames, width, height, opt.subsampling, d_out,
                      out_stride, d_out_len, frame_stride)
-        _check(lib().dmmt_encode_device_ycc(self._ctx, ctypes.byref(y), ctypes.byref(opt), stream),
-               "encode_device_ycc")
+        if levels is None:
+            _check(lib().dmmt_encode_device_ycc(self._ctx, ctypes.byref(y), ctypes.byref(opt), stream),
+                   "encode_device_ycc")
+        else:
+            _check(lib().dmmt_encode_device_ycc_levels(self._ctx, ctypes.byref(y), ctypes.byref(levels),
+                                                       ctypes.byref(opt), stream), "encode_device_ycc_levels")
 
-    def encode_ycc(self, y, cb=None, cr=None, uv=None, vu=None, options: JpegTransformationOptions = None) -> bytes:
+    def encode_ycc(self, y, cb=None, cr=None, uv=None, vu=None, options: JpegTransformationOptions = None,
+                   bit_depth: int = 8, shift: int = 0, range: int = YccRange.FULL) -> bytes:
         """One frame from host planes (numpy uint8, JFIF full range): y (H, W) with cb
         and cr (ch, cw) each, or uv / vu (ch, cw, 2) -- Cb,Cr / Cr,Cb pairs; ch =
         ceil(H / vr), cw = ceil(W / hr) for options.chroma_subsampling_preset.  The
-        planes are uploaded, encoded where they lie (no RGB round trip) and freed."""
+        planes are uploaded, encoded where they lie (no RGB round trip) and freed.
+        Other levels: range=YccRange.LIMITED, and uint16 planes of bit_depth (8..16)
+        significant bits above `shift` unused low bits (P010: bit_depth 10, shift 6)."""
         if options is None:
             options = JpegTransformationOptions()
         given = [k for k, v in (("cb", cb), ("cr", cr), ("uv", uv), ("vu", vu)) if v is not None]
@@ -655,8 +687,12 @@ class Encoder:
             raise ValueError("give cb and cr, or uv, or vu")
         sub = ChromaSubsamplingPreset(options.chroma_subsampling_preset)
         planes = [np.asarray(p) for p in [y] + chroma]
-        if any(p.dtype != np.uint8 for p in planes):
-            raise ValueError("uint8 planes are required")
+        dtype = planes[0].dtype
+        if dtype not in (np.uint8, np.uint16) or any(p.dtype != dtype for p in planes):
+            raise ValueError("uint8 planes are required, or uint16 planes with bit_depth / shift")
+        sb = dtype.itemsize
+        plain = sb == 1 and bit_depth == 8 and shift == 0 and int(range) == YccRange.FULL
+        levels = None if plain else DmmtYccLevels(int(range), int(bit_depth), sb, int(shift))
         if planes[0].ndim != 2 or 0 in planes[0].shape:
             raise ValueError("y: shape (H, W)")
         h, w = planes[0].shape
@@ -671,14 +707,14 @@ class Encoder:
         ptrs = []
         try:
             for p in planes:
-                ptrs.append(self.malloc(p.size))
+                ptrs.append(self.malloc(p.nbytes))
                 self.h2d(ptrs[-1], p)
             d_out = self.malloc(cap)
             ptrs.append(d_out)
             d_len = self.malloc(4)
             ptrs.append(d_len)
-            self.encode_device_ycc(ptrs[:len(planes)], fmt, w, planes[1].size // ch, 1, w, h, options, d_out, cap,
-                                   d_len)
+            self.encode_device_ycc(ptrs[:len(planes)], fmt, w * sb, planes[1].nbytes // ch, 1, w, h, options, d_out,
+                                   cap, d_len, levels=levels)
             self.synchronize()
             n = int(np.frombuffer(self.d2h(d_len, 4), np.uint32)[0])
             return self.d2h(d_out, min(n, cap))

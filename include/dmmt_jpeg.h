@@ -198,7 +198,8 @@ size_t dmmt_surface_span(const dmmt_device_surfaces* surfaces);
  * their Cr,Cb twins).  The reference has no such input (Image<f32> is always RGB), so the
  * contract is stated in its stages, with hr, vr the rates of opt->subsampling:
  *  - samples are uint8, JFIF full range (Y, Cb, Cr in 0..255, chroma centred on 128).  NO range
- *    conversion is done: limited ("video") range input is encoded as if it were full range;
+ *    conversion is done: limited ("video") range input is encoded as if it were full range
+ *    (dmmt_encode_device_ycc_levels below converts it, and takes 10- to 16-bit planes);
  *  - the luma plane is width x height, each chroma component ceil(width/hr) x ceil(height/vr).
  *    The chroma is taken as given: no resampling, no averaging.  chroma_sampling says how the
  *    planes lie and must equal opt->subsampling: conversion between samplings is out of
@@ -237,6 +238,64 @@ int dmmt_encode_device_ycc(dmmt_ctx* ctx, const dmmt_device_ycc* ycc, const dmmt
  * (a chroma row: ceil(width/hr) bytes planar, twice that for NV*); 0 for an unsupported
  * description or a plane the format does not use */
 size_t dmmt_ycc_plane_span(const dmmt_device_ycc* ycc, int plane);
+
+/* ---- YCbCr sample levels: limited range, 10- to 16-bit planes (extension) ---------------------
+ * What decoders and camera pipelines usually hand over: limited ("video") range (Y 16..235,
+ * chroma 16..240 at 8 bits) and more than 8 bits in a uint16 -- P010 / P012 / P016 with the
+ * bits at the top of the word, I010 / yuv420p10le with the bits at the bottom.
+ * dmmt_encode_device_ycc_levels takes dmmt_encode_device_ycc's plane description plus the
+ * sample levels and converts each sample to the JFIF full-range value inside the front
+ * kernel, in f32, with no 8-bit rounding in between; everything else is that call's contract.
+ *
+ *   format                  bit_depth  sample_bytes  shift
+ *   P010                    10         2             6
+ *   P012                    12         2             4
+ *   P016 / I016             16         2             0
+ *   I010 / yuv420p10le      10         2             0
+ *   8-bit limited NV12       8         1             0
+ *
+ *  - levels == NULL means {DMMT_YCC_RANGE_FULL, 8, 1, 0}: the call then behaves exactly as
+ *    dmmt_encode_device_ycc and produces the same bytes.  Valid levels: range FULL or LIMITED;
+ *    sample_bytes 1 with bit_depth 8 and shift 0, or sample_bytes 2 with bit_depth B in 8..16
+ *    and shift in 0..16-B; anything else is DMMT_E_INVALID_ARGUMENT;
+ *  - in dmmt_device_ycc, pitches, frame_stride and spans stay in BYTES.  With sample_bytes 2,
+ *    both pitches, frame_stride and every plane pointer are multiples of 2, else
+ *    DMMT_E_INVALID_ARGUMENT.  A luma row is width * sample_bytes bytes, a chroma row
+ *    ceil(width/hr) * sample_bytes bytes, twice that for NV*; the pitches are at least that.
+ *    dmmt_ycc_plane_span_levels returns (rows-1)*pitch + row bytes, or 0 for an unsupported
+ *    description (levels included) or a plane the format does not use;
+ *  - the read guarantee is dmmt_encode_device_ycc's with that span: for plane p and frame f only
+ *    bytes of [d_plane[p] + f * frame_stride, ... + dmmt_ycc_plane_span_levels(y, levels, p)) are
+ *    read, and only the rectangle's samples influence the output or the error check;
+ *  - a uint16 sample s (host endian) carries the code v = s >> shift: its low `shift` bits are
+ *    ignored (some decoders leave garbage there).  A code v > 2^B - 1 inside the rectangle --
+ *    possible only when shift < 16 - B -- reports DMMT_E_VALUE_EXCEEDS_MAX through
+ *    dmmt_ctx_synchronize, as a sample above maxval does for the RGB calls; the same value in
+ *    pitch padding or outside the rectangle is not an error;
+ *  - the transfer, all in IEEE f32, every operation rounded once, nothing fused.  With
+ *    m = 2^(B-8) the library computes on the host
+ *        FULL:     offY = 0,     kY = 255 / (2^B - 1),  offC = 2^(B-1),  kC = kY
+ *        LIMITED:  offY = 16 m,  kY = 255 / (219 m),    offC = 128 m,    kC = 255 / (224 m)
+ *    and a code v enters the DCT as
+ *        luma    min(max(((float)v - offY) * kY, 0), 255) - 128
+ *        chroma  min(max(((float)v - offC) * kC, -128), 127)
+ *    so codes below black or above white clamp, and for B = 8, FULL this is v - 128 exactly,
+ *    dmmt_encode_device_ycc's contract.  No matrix or primaries conversion is done: the file is
+ *    written with whatever matrix the planes carry;
+ *  - padding is black after the transfer: luma -128, chroma 0;
+ *  - stream, lanes, errors and chroma_sampling == opt->subsampling as dmmt_encode_device_ycc;
+ *    the call invalidates a pending stripe like every other encoding call; a multi-GPU
+ *    context: member 0. */
+enum dmmt_ycc_range { DMMT_YCC_RANGE_FULL = 0, DMMT_YCC_RANGE_LIMITED = 1 };
+typedef struct dmmt_ycc_levels {
+    int32_t range;        /* dmmt_ycc_range */
+    int32_t bit_depth;    /* B: 8 with sample_bytes 1; 8..16 with sample_bytes 2 */
+    int32_t sample_bytes; /* 1: uint8; 2: uint16, host endian */
+    int32_t shift;        /* unused low bits of a uint16 sample, 0..16-B: code v = s >> shift */
+} dmmt_ycc_levels;
+int dmmt_encode_device_ycc_levels(dmmt_ctx* ctx, const dmmt_device_ycc* ycc, const dmmt_ycc_levels* levels,
+                                  const dmmt_options* opt, void* stream);
+size_t dmmt_ycc_plane_span_levels(const dmmt_device_ycc* ycc, const dmmt_ycc_levels* levels, int plane);
 
 /* ---- grayscale frames (extension) -----------------------------------------------------------
  * One-channel frames -- a mono camera, an IR or depth sensor, a scanned page, the Y plane of a
