@@ -455,12 +455,14 @@ int enqueue_back_half(dmmt_ctx* c, const Geom& g, int nf, const Work& w, int bit
 int enqueue_direct(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, int nf, const Geom& g,
                    const Work& w, int bits, uint8_t* out, size_t out_stride, uint32_t* out_len, hipStream_t st,
                    const Surface* sf = nullptr, const YccFrames* yf = nullptr, const GrayPlane* gp = nullptr,
-                   const YccLevels* lv = nullptr) {
+                   const YccLevels* lv = nullptr, const YccMatrix* mx = nullptr) {
     {
         StageTimer t(c, ST_FRONT, st);
         const int cap = c->nlanes > 1 ? DMMT_FRONT_PER_CU_LANES : 0;
         if (gp)  // a one-channel plane: d_rgb is the plane
             HIP_TRY(launch_front_gray(*gp, frame_stride, sb, nf, g, w, st, cap));
+        else if (yf && lv && mx)  // YCbCr planes of another matrix than JFIF's (lv: any levels)
+            HIP_TRY(launch_front_ycc_matrix(*yf, *lv, *mx, frame_stride, nf, g, w, st, cap));
         else if (yf && lv)  // YCbCr planes of other levels than uint8 full range
             HIP_TRY(launch_front_ycc_levels(*yf, *lv, frame_stride, nf, g, w, st, cap));
         else if (yf)  // YCbCr planes (uint8): d_rgb is the luma plane
@@ -485,7 +487,8 @@ void destroy_graphs(dmmt_ctx* c) {
 int enqueue_encode(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, int nf, const Geom& g,
                    const dmmt_options* opt, uint8_t* out, size_t out_stride, uint32_t* out_len, hipStream_t st,
                    int lane = 0, bool async = false, int* status = nullptr, const Surface* sf = nullptr,
-                   const YccFrames* yf = nullptr, const GrayPlane* gray = nullptr, const YccLevels* lv = nullptr) {
+                   const YccFrames* yf = nullptr, const GrayPlane* gray = nullptr, const YccLevels* lv = nullptr,
+                   const YccMatrix* mx = nullptr, int matrix = 0) {
     Work w;
     int rc;
     if ((rc = prepare(c, g, nf, opt, sb, st, &w, lane, async, status, true))) return rc;
@@ -501,7 +504,7 @@ int enqueue_encode(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, 
     // (a per-file status area -- dmmt_convert_ppm_device_batch -- would put a new
     // pointer into every file's graph key: that path launches directly)
     if (!c->use_graphs || c->profile || status)
-        return enqueue_direct(c, d_rgb, frame_stride, sb, nf, g, w, bits, out, out_stride, out_len, st, sf, yf, gp, lv);
+        return enqueue_direct(c, d_rgb, frame_stride, sb, nf, g, w, bits, out, out_stride, out_len, st, sf, yf, gp, lv, mx);
     std::vector<uint64_t> key = {(uint64_t)(uintptr_t)d_rgb, (uint64_t)frame_stride, (uint64_t)sb, (uint64_t)nf,
                                  (uint64_t)g.width, (uint64_t)g.height, (uint64_t)g.hr, (uint64_t)g.vr,
                                  (uint64_t)g.maxval, (uint64_t)g.restart_interval, (uint64_t)bits,
@@ -517,6 +520,8 @@ int enqueue_encode(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, 
     if (lv)  // the same planes and pitches read as other levels are another front kernel or other arguments
         key.insert(key.end(), {(uint64_t)lv->range + 64, (uint64_t)lv->bit_depth, (uint64_t)lv->sample_bytes,
                                (uint64_t)lv->shift});
+    if (mx)  // the same planes and levels under another matrix are another front kernel or other arguments
+        key.push_back((uint64_t)matrix + 128);
     // a gray call and a 4:4:4 colour call of the same size share every field above: the
     // component count, the transfer (through the table's contents the graph reads, and the
     // table's address), the plane and its pitch
@@ -533,7 +538,7 @@ int enqueue_encode(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, 
     if (!hit) {
         hipGraph_t graph = nullptr;
         HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        rc = enqueue_direct(c, d_rgb, frame_stride, sb, nf, g, w, bits, out, out_stride, out_len, st, sf, yf, gp, lv);
+        rc = enqueue_direct(c, d_rgb, frame_stride, sb, nf, g, w, bits, out, out_stride, out_len, st, sf, yf, gp, lv, mx);
         hipError_t e = hipStreamEndCapture(st, &graph);
         if (rc) {
             if (graph) (void)hipGraphDestroy(graph);
@@ -796,11 +801,13 @@ extern "C" size_t dmmt_max_jpeg_bytes(uint16_t width, uint16_t height, int32_t s
 
 // dmmt_encode_device, dmmt_encode_device_surfaces (sf: the surface, whose first
 // plane is f->d_rgb) and dmmt_encode_device_ycc[_levels] (yf: the planes, f->d_rgb
-// the luma plane; lv: their levels unless uint8 full range) after their own
-// argument checks
+// the luma plane; lv: their levels unless uint8 full range; mx: the step to BT.601
+// of dmmt_encode_device_ycc_matrix, then lv is set whatever the levels) after their
+// own argument checks
 static int encode_device_frames(dmmt_ctx* c, const dmmt_device_frames* f, const dmmt_options* opt, void* stream,
                                 const Geom& g, const Surface* sf, const YccFrames* yf = nullptr,
-                                const GrayPlane* gp = nullptr, const YccLevels* lv = nullptr) {
+                                const GrayPlane* gp = nullptr, const YccLevels* lv = nullptr,
+                                const YccMatrix* mx = nullptr, int matrix = 0) {
     int rc;
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = set_device(c))) return rc;
@@ -811,7 +818,7 @@ static int encode_device_frames(dmmt_ctx* c, const dmmt_device_frames* f, const 
         HIP_TRY(hipEventRecord(c->ev_lane0, c->stream));
         HIP_TRY(hipStreamWaitEvent(st, c->ev_lane0, 0));
         rc = enqueue_encode(c, f->d_rgb, f->frame_stride, f->sample_bytes, f->n_frames, g, opt, f->d_out,
-                            f->out_stride, f->d_out_len, st, 0, true, nullptr, sf, yf, gp, lv);
+                            f->out_stride, f->d_out_len, st, 0, true, nullptr, sf, yf, gp, lv, mx, matrix);
         HIP_TRY(hipEventRecord(c->ev_caller, st));
         HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_caller, 0));
         return rc;
@@ -819,7 +826,7 @@ static int encode_device_frames(dmmt_ctx* c, const dmmt_device_frames* f, const 
     int lane = 0;  // pipelined: the next lane's workspace and stream
     if (c->nlanes > 1) lane = (int)(c->next_lane++ % (unsigned)c->nlanes);
     return enqueue_encode(c, f->d_rgb, f->frame_stride, f->sample_bytes, f->n_frames, g, opt, f->d_out, f->out_stride,
-                          f->d_out_len, c->lanes[lane]->stream, lane, true, nullptr, sf, yf, gp, lv);
+                          f->d_out_len, c->lanes[lane]->stream, lane, true, nullptr, sf, yf, gp, lv, mx, matrix);
 }
 
 extern "C" int dmmt_encode_device(dmmt_ctx* c, const dmmt_device_frames* f, const dmmt_options* opt, void* stream) {
@@ -901,10 +908,22 @@ extern "C" size_t dmmt_ycc_plane_span(const dmmt_device_ycc* y, int plane) {
     return dmmt_ycc_plane_span_levels(y, nullptr, plane);
 }
 
-extern "C" int dmmt_encode_device_ycc_levels(dmmt_ctx* c, const dmmt_device_ycc* y, const dmmt_ycc_levels* levels,
-                                             const dmmt_options* opt, void* stream) {
+extern "C" int dmmt_ycc_matrix_coefficients(int32_t matrix, float m[6]) {
+    YccMatrix mx;
+    if (!m || !ycc_matrix_coefficients(matrix, &mx)) return DMMT_E_INVALID_ARGUMENT;
+    m[0] = mx.a, m[1] = mx.b, m[2] = mx.c, m[3] = mx.d, m[4] = mx.e, m[5] = mx.f;
+    return DMMT_OK;
+}
+
+extern "C" int dmmt_encode_device_ycc_matrix(dmmt_ctx* c, const dmmt_device_ycc* y, const dmmt_ycc_levels* levels,
+                                             int32_t matrix, const dmmt_options* opt, void* stream) {
     c = primary(c);
     if (!c || !y) return DMMT_E_INVALID_ARGUMENT;
+    // JFIF: the planes are written as they are, by the kernels and under the graph keys of
+    // dmmt_encode_device_ycc[_levels]; never through the matrix kernel
+    YccMatrix mx{};
+    const bool convert = matrix != DMMT_YCC_MATRIX_JFIF;
+    if (convert && !ycc_matrix_coefficients(matrix, &mx)) return DMMT_E_INVALID_ARGUMENT;
     int rc;
     if ((rc = validate(opt))) return rc;
     if (y->n_frames <= 0 || !y->d_out || !y->d_out_len) return DMMT_E_INVALID_ARGUMENT;
@@ -938,7 +957,14 @@ extern "C" int dmmt_encode_device_ycc_levels(dmmt_ctx* c, const dmmt_device_ycc*
     f.n_frames = y->n_frames;
     f.width = y->width, f.height = y->height, f.maxval = 255, f.sample_bytes = 1;
     f.d_out = y->d_out, f.out_stride = y->out_stride, f.d_out_len = y->d_out_len;
+    if (convert)  // (the matrix kernel takes every levels, uint8 full range included)
+        return encode_device_frames(c, &f, opt, stream, g, nullptr, &yf, nullptr, &lv, &mx, matrix);
     return encode_device_frames(c, &f, opt, stream, g, nullptr, &yf, nullptr, plain ? nullptr : &lv);
+}
+
+extern "C" int dmmt_encode_device_ycc_levels(dmmt_ctx* c, const dmmt_device_ycc* y, const dmmt_ycc_levels* levels,
+                                             const dmmt_options* opt, void* stream) {
+    return dmmt_encode_device_ycc_matrix(c, y, levels, DMMT_YCC_MATRIX_JFIF, opt, stream);
 }
 
 extern "C" int dmmt_encode_device_ycc(dmmt_ctx* c, const dmmt_device_ycc* y, const dmmt_options* opt, void* stream) {

@@ -94,6 +94,21 @@ size_t ycc_plane_span_levels(int format, int plane, int width, int height, int h
 hipError_t launch_front_ycc_levels(const YccFrames& yf, const YccLevels& lv, size_t frame_stride_bytes, int n_frames,
                                    const Geom& g, const Work& w, hipStream_t st, int per_cu_cap = 0);
 
+// The matrix YCbCr planes carry (dmmt_ycc_matrix); JFIF is BT.601, no conversion
+enum { YCC_MATRIX_JFIF = 0, YCC_MATRIX_BT709 = 1, YCC_MATRIX_BT2020 = 2 };
+// the step to BT.601 after the transfer, in f32, each operation rounded once, clamped to
+// [-128, 127]: Y' = (y + a cb) + b cr, Cb' = c cb + d cr, Cr' = e cb + f cr
+struct YccMatrix {
+    float a, b, c, d, e, f;
+};
+// the six constants of BT709 or BT2020 (host, double precision rounded once); false:
+// another matrix, JFIF included
+bool ycc_matrix_coefficients(int matrix, YccMatrix* out);
+// k_front_ycc_mx (front_ycc_matrix.hip): launch_front_ycc_levels with that step
+hipError_t launch_front_ycc_matrix(const YccFrames& yf, const YccLevels& lv, const YccMatrix& mx,
+                                   size_t frame_stride_bytes, int n_frames, const Geom& g, const Work& w,
+                                   hipStream_t st, int per_cu_cap = 0);
+
 // A one-channel plane (dmmt_device_gray): transfer as dmmt_gray_transfer
 enum { GRAY_AS_RGB = 0, GRAY_Y_FULL_RANGE = 1 };
 struct GrayPlane {

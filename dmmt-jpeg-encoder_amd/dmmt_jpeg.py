@@ -94,6 +94,8 @@ def lib():
     L.dmmt_encode_device_ycc_levels.argtypes = [vp, P(DmmtDeviceYcc), P(DmmtYccLevels), P(DmmtOptions), vp]
     L.dmmt_ycc_plane_span_levels.argtypes = [P(DmmtDeviceYcc), P(DmmtYccLevels), ctypes.c_int]
     L.dmmt_ycc_plane_span_levels.restype = sz
+    L.dmmt_encode_device_ycc_matrix.argtypes = [vp, P(DmmtDeviceYcc), P(DmmtYccLevels), i32, P(DmmtOptions), vp]
+    L.dmmt_ycc_matrix_coefficients.argtypes = [i32, P(ctypes.c_float)]
     L.dmmt_encode_device_gray.argtypes = [vp, P(DmmtDeviceGray), P(DmmtOptions), vp]
     L.dmmt_gray_span.argtypes = [P(DmmtDeviceGray)]
     L.dmmt_gray_span.restype = sz
@@ -246,6 +248,21 @@ def ycc_plane_span_levels(y: DmmtDeviceYcc, levels: DmmtYccLevels | None, plane:
     for samples of these levels (None: uint8 full range)"""
     return int(lib().dmmt_ycc_plane_span_levels(ctypes.byref(y), ctypes.byref(levels) if levels is not None else None,
                                                 int(plane)))
+
+
+class YccMatrix(enum.IntEnum):
+    """dmmt_ycc_matrix: the matrix YCbCr planes carry"""
+    JFIF = 0    # BT.601, what a JFIF file is decoded with: the planes are written as they are
+    BT709 = 1   # HD and 4K decoders
+    BT2020 = 2  # HDR / UHD pipelines, non-constant luminance
+
+
+def ycc_matrix_coefficients(matrix: int) -> tuple:
+    """dmmt_ycc_matrix_coefficients: the f32 constants a, b, c, d, e, f of the step that
+    takes BT709 or BT2020 values to the JFIF matrix (JFIF itself has none: Error)"""
+    m = (ctypes.c_float * 6)()
+    _check(lib().dmmt_ycc_matrix_coefficients(int(matrix), m), "ycc_matrix_coefficients")
+    return tuple(float(x) for x in m)
 
 
 class DmmtDeviceGray(ctypes.Structure):
@@ -651,15 +668,22 @@ class Encoder:
     def encode_device_ycc(self, d_planes, fmt: int, luma_pitch: int, chroma_pitch: int, n_frames: int, width: int,
                           height: int, options: JpegTransformationOptions, d_out: int, out_stride: int,
                           d_out_len: int, frame_stride: int = 0, stream: int | None = None,
-                          opt_c: DmmtOptions | None = None, levels: DmmtYccLevels | None = None):
+                          opt_c: DmmtOptions | None = None, levels: DmmtYccLevels | None = None,
+                          matrix: int = YccMatrix.JFIF):
         """dmmt_encode_device_ycc: uint8 full-range YCbCr planes in HBM, subsampled as
         options.chroma_subsampling_preset says; enqueued, see synchronize().  levels:
         dmmt_encode_device_ycc_levels -- limited range, 8 to 16 bits in uint16 samples
-        (pitches and frame_stride stay in bytes)"""
+        (pitches and frame_stride stay in bytes).  matrix: dmmt_encode_device_ycc_matrix --
+        BT709 or BT2020 planes are taken to the JFIF matrix on the way"""
         opt = opt_c if opt_c is not None else options.to_c()
         y = self.ycc(d_planes, fmt, luma_pitch, chroma_pitch, n_frames, width, height, opt.subsampling, d_out,
                      out_stride, d_out_len, frame_stride)
-        if levels is None:
+        if int(matrix) != YccMatrix.JFIF:
+            _check(lib().dmmt_encode_device_ycc_matrix(self._ctx, ctypes.byref(y),
+                                                       ctypes.byref(levels) if levels is not None else None,
+                                                       int(matrix), ctypes.byref(opt), stream),
+                   "encode_device_ycc_matrix")
+        elif levels is None:
             _check(lib().dmmt_encode_device_ycc(self._ctx, ctypes.byref(y), ctypes.byref(opt), stream),
                    "encode_device_ycc")
         else:
@@ -667,13 +691,15 @@ class Encoder:
                                                        ctypes.byref(opt), stream), "encode_device_ycc_levels")
 
     def encode_ycc(self, y, cb=None, cr=None, uv=None, vu=None, options: JpegTransformationOptions = None,
-                   bit_depth: int = 8, shift: int = 0, range: int = YccRange.FULL) -> bytes:
+                   bit_depth: int = 8, shift: int = 0, range: int = YccRange.FULL,
+                   matrix: int = YccMatrix.JFIF) -> bytes:
         """One frame from host planes (numpy uint8, JFIF full range): y (H, W) with cb
         and cr (ch, cw) each, or uv / vu (ch, cw, 2) -- Cb,Cr / Cr,Cb pairs; ch =
         ceil(H / vr), cw = ceil(W / hr) for options.chroma_subsampling_preset.  The
         planes are uploaded, encoded where they lie (no RGB round trip) and freed.
         Other levels: range=YccRange.LIMITED, and uint16 planes of bit_depth (8..16)
-        significant bits above `shift` unused low bits (P010: bit_depth 10, shift 6)."""
+        significant bits above `shift` unused low bits (P010: bit_depth 10, shift 6).
+        matrix: YccMatrix.BT709 / BT2020 planes are taken to the JFIF matrix."""
         if options is None:
             options = JpegTransformationOptions()
         given = [k for k, v in (("cb", cb), ("cr", cr), ("uv", uv), ("vu", vu)) if v is not None]
@@ -714,7 +740,7 @@ class Encoder:
             d_len = self.malloc(4)
             ptrs.append(d_len)
             self.encode_device_ycc(ptrs[:len(planes)], fmt, w * sb, planes[1].nbytes // ch, 1, w, h, options, d_out,
-                                   cap, d_len, levels=levels)
+                                   cap, d_len, levels=levels, matrix=matrix)
             self.synchronize()
             n = int(np.frombuffer(self.d2h(d_len, 4), np.uint32)[0])
             return self.d2h(d_out, min(n, cap))

@@ -281,7 +281,8 @@ size_t dmmt_ycc_plane_span(const dmmt_device_ycc* ycc, int plane);
  *        chroma  min(max(((float)v - offC) * kC, -128), 127)
  *    so codes below black or above white clamp, and for B = 8, FULL this is v - 128 exactly,
  *    dmmt_encode_device_ycc's contract.  No matrix or primaries conversion is done: the file is
- *    written with whatever matrix the planes carry;
+ *    written with whatever matrix the planes carry (dmmt_encode_device_ycc_matrix below takes
+ *    BT.709 and BT.2020 planes to the JFIF matrix);
  *  - padding is black after the transfer: luma -128, chroma 0;
  *  - stream, lanes, errors and chroma_sampling == opt->subsampling as dmmt_encode_device_ycc;
  *    the call invalidates a pending stripe like every other encoding call; a multi-GPU
@@ -296,6 +297,49 @@ typedef struct dmmt_ycc_levels {
 int dmmt_encode_device_ycc_levels(dmmt_ctx* ctx, const dmmt_device_ycc* ycc, const dmmt_ycc_levels* levels,
                                   const dmmt_options* opt, void* stream);
 size_t dmmt_ycc_plane_span_levels(const dmmt_device_ycc* ycc, const dmmt_ycc_levels* levels, int plane);
+
+/* ---- YCbCr matrix: BT.709 and BT.2020 planes to the JFIF matrix (extension) --------------------
+ * A JFIF file is decoded with the BT.601 matrix (Kr 0.299, Kb 0.114).  HD and 4K decoders hand
+ * over BT.709 planes, HDR / UHD pipelines BT.2020 (non-constant luminance); written as they are,
+ * such planes give files whose colours every viewer shows wrong.  dmmt_encode_device_ycc_matrix
+ * is dmmt_encode_device_ycc_levels with one step added after the transfer, inside the front
+ * kernel: no RGB round trip, no plane read twice, no extra pass.  Planes, pitches, spans, the
+ * read guarantee, levels (NULL as before), the DMMT_E_VALUE_EXCEEDS_MAX check, lanes, streams,
+ * stripe invalidation and member 0 of a multi-GPU context are that call's in every respect.
+ *  - matrix DMMT_YCC_MATRIX_JFIF: no step; the call IS dmmt_encode_device_ycc_levels (the same
+ *    kernels, the same bytes), which in turn is this call with JFIF.  Any value other than the
+ *    three below is DMMT_E_INVALID_ARGUMENT;
+ *  - the constants.  With the source's Kr, Kb, Kg = 1 - Kr - Kb (BT.709: 0.2126, 0.0722;
+ *    BT.2020: 0.2627, 0.0593) and the target's Kr' = 0.299, Kb' = 0.114, Kg' = 0.587 the
+ *    library computes on the host, in double precision, each rounded once to f32
+ *        a = Kb' 2(1-Kb) - Kg' 2Kb(1-Kb)/Kg        b = Kr' 2(1-Kr) - Kg' 2Kr(1-Kr)/Kg
+ *        c = (2(1-Kb) - a) / (2(1-Kb'))            d = -b / (2(1-Kb'))
+ *        e = -a / (2(1-Kr'))                       f = (2(1-Kr) - b) / (2(1-Kr'))
+ *    (dmmt_ycc_matrix_coefficients returns them as m[0..5]; DMMT_E_INVALID_ARGUMENT for JFIF,
+ *    which has none, for an unknown matrix and for m == NULL);
+ *  - the step.  With y, cb, cr the values dmmt_encode_device_ycc_levels feeds the DCT (level-
+ *    shifted, clamped, in [-128, 127]), in IEEE f32, every operation rounded once, nothing
+ *    fused, in this order:
+ *        Y'  = min(max((y + a*cb) + b*cr, -128), 127)
+ *        Cb' = min(max(c*cb + d*cr, -128), 127)
+ *        Cr' = min(max(e*cb + f*cr, -128), 127)
+ *    so grey stays grey and out-of-gamut results clamp;
+ *  - with subsampled chroma the luma sample at (x, y) uses the chroma position (x / hr, y / vr),
+ *    the one that shares its MCU cell; chroma is neither interpolated nor re-sited;
+ *  - padding is black after the matrix: every luma sample outside the width x height rectangle
+ *    is -128 whatever chroma sample shares its cell (odd widths and heights make such cells),
+ *    chroma padding is 0;
+ *  - out of scope: primaries and transfer functions (BT.2020 gamut mapping, PQ / HLG) -- only
+ *    the matrix is converted --, chroma interpolation or re-siting, conversion between
+ *    samplings, and a host entry point for YCbCr planes. */
+enum dmmt_ycc_matrix {
+    DMMT_YCC_MATRIX_JFIF   = 0,  /* BT.601: the planes are written as they are */
+    DMMT_YCC_MATRIX_BT709  = 1,
+    DMMT_YCC_MATRIX_BT2020 = 2   /* non-constant luminance */
+};
+int dmmt_encode_device_ycc_matrix(dmmt_ctx* ctx, const dmmt_device_ycc* ycc, const dmmt_ycc_levels* levels,
+                                  int32_t matrix, const dmmt_options* opt, void* stream);
+int dmmt_ycc_matrix_coefficients(int32_t matrix, float m[6]);
 
 /* ---- grayscale frames (extension) -----------------------------------------------------------
  * One-channel frames -- a mono camera, an IR or depth sensor, a scanned page, the Y plane of a
