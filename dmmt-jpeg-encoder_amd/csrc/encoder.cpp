@@ -461,12 +461,9 @@ int enqueue_direct(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, 
         const int cap = c->nlanes > 1 ? DMMT_FRONT_PER_CU_LANES : 0;
         if (gp)  // a one-channel plane: d_rgb is the plane
             HIP_TRY(launch_front_gray(*gp, frame_stride, sb, nf, g, w, st, cap));
-        else if (yf && lv && mx)  // YCbCr planes of another matrix than JFIF's (lv: any levels)
-            HIP_TRY(launch_front_ycc_matrix(*yf, *lv, *mx, frame_stride, nf, g, w, st, cap));
-        else if (yf && lv)  // YCbCr planes of other levels than uint8 full range
-            HIP_TRY(launch_front_ycc_levels(*yf, *lv, frame_stride, nf, g, w, st, cap));
-        else if (yf)  // YCbCr planes (uint8): d_rgb is the luma plane
-            HIP_TRY(launch_front_ycc(*yf, frame_stride, nf, g, w, st, cap));
+        else if (yf)  // YCbCr planes: d_rgb is the luma plane; lv: other levels than uint8 full
+                      // range; mx (with lv, any levels): another matrix than JFIF's
+            HIP_TRY(launch_front_ycc(*yf, lv, mx, frame_stride, nf, g, w, st, cap));
         else if (sf)  // a surface: d_rgb is its first plane
             HIP_TRY(launch_front_surface(*sf, frame_stride, sb, nf, g, w, st, cap));
         else

@@ -67,10 +67,6 @@ struct YccFrames {
 // format or a plane the format does not use
 size_t ycc_plane_span(int format, int plane, int width, int height, int hr, int vr, size_t luma_pitch,
                       size_t chroma_pitch);
-// k_front_ycc (front_ycc.hip): uint8 full-range planes -> w.coef, as launch_front;
-// the chroma sampling of the planes is g's
-hipError_t launch_front_ycc(const YccFrames& yf, size_t frame_stride_bytes, int n_frames, const Geom& g, const Work& w,
-                            hipStream_t st, int per_cu_cap = 0);
 
 // The sample levels of YCbCr frames (dmmt_ycc_levels): range as dmmt_ycc_range
 enum { YCC_RANGE_FULL = 0, YCC_RANGE_LIMITED = 1 };
@@ -82,17 +78,13 @@ struct YccLevels {
 struct YccTransfer {
     float off_y, k_y, off_c, k_c;
 };
-// a description the levels kernels take: uint8 with 8 bits, uint16 with 8..16 bits
+// a description k_front_ycc takes: uint8 with 8 bits, uint16 with 8..16 bits
 // and shift <= 16 - bits
 bool ycc_levels_valid(const YccLevels& lv);
 YccTransfer ycc_levels_transfer(const YccLevels& lv);  // (host; lv valid)
 // ycc_plane_span with sample_bytes bytes per sample (0: not 1 or 2)
 size_t ycc_plane_span_levels(int format, int plane, int width, int height, int hr, int vr, size_t luma_pitch,
                              size_t chroma_pitch, int sample_bytes);
-// k_front_ycc_lv (front_ycc_levels.hip): planes of any valid levels -> w.coef, as
-// launch_front_ycc; a code above 2^bits - 1 raises status bit 1
-hipError_t launch_front_ycc_levels(const YccFrames& yf, const YccLevels& lv, size_t frame_stride_bytes, int n_frames,
-                                   const Geom& g, const Work& w, hipStream_t st, int per_cu_cap = 0);
 
 // The matrix YCbCr planes carry (dmmt_ycc_matrix); JFIF is BT.601, no conversion
 enum { YCC_MATRIX_JFIF = 0, YCC_MATRIX_BT709 = 1, YCC_MATRIX_BT2020 = 2 };
@@ -104,10 +96,12 @@ struct YccMatrix {
 // the six constants of BT709 or BT2020 (host, double precision rounded once); false:
 // another matrix, JFIF included
 bool ycc_matrix_coefficients(int matrix, YccMatrix* out);
-// k_front_ycc_mx (front_ycc_matrix.hip): launch_front_ycc_levels with that step
-hipError_t launch_front_ycc_matrix(const YccFrames& yf, const YccLevels& lv, const YccMatrix& mx,
-                                   size_t frame_stride_bytes, int n_frames, const Geom& g, const Work& w,
-                                   hipStream_t st, int per_cu_cap = 0);
+// k_front_ycc (front_ycc.hip): the planes -> w.coef, as launch_front; their chroma
+// sampling is g's.  lv null: uint8 full range (the plain instantiations); else any
+// valid levels, and a code above 2^bits - 1 raises status bit 1.  mx (needs lv):
+// that step after the transfer; null: none
+hipError_t launch_front_ycc(const YccFrames& yf, const YccLevels* lv, const YccMatrix* mx, size_t frame_stride_bytes,
+                            int n_frames, const Geom& g, const Work& w, hipStream_t st, int per_cu_cap = 0);
 
 // A one-channel plane (dmmt_device_gray): transfer as dmmt_gray_transfer
 enum { GRAY_AS_RGB = 0, GRAY_Y_FULL_RANGE = 1 };

@@ -18,7 +18,7 @@
 // reference's black padding (padder.rs:12-42) in YCbCr.  Phase A needs no bounds
 // checks.
 //
-// SB: bytes per sample, 1 (uint8) or 2 (uint16, front_ycc_levels.hip; every pitch,
+// SB: bytes per sample, 1 (uint8) or 2 (uint16, the levels and matrix kinds; every pitch,
 // plane address and so every offset and misalignment even).  Every byte count above
 // scales with it: a luma tile row is 256 * SB bytes, a chroma position SB or 2 * SB
 // bytes.  The pad samples are then the caller's (luma_fill, chroma_fill: the code
