@@ -514,6 +514,8 @@ int enqueue_encode(dmmt_ctx* c, const void* d_rgb, size_t frame_stride, int sb, 
     if (yf)  // YCbCr planes: two descriptions may share their luma pointer
         key.insert(key.end(), {(uint64_t)yf->format + 16, (uint64_t)yf->luma_pitch, (uint64_t)yf->chroma_pitch,
                                (uint64_t)(uintptr_t)yf->plane[1], (uint64_t)(uintptr_t)yf->plane[2]});
+    if (yf && yf->src_hr)  // the same planes read at a finer sampling than the file's: the converting kernel
+        key.insert(key.end(), {(uint64_t)yf->src_hr + 256, (uint64_t)yf->src_vr});
     if (lv)  // the same planes and pitches read as other levels are another front kernel or other arguments
         key.insert(key.end(), {(uint64_t)lv->range + 64, (uint64_t)lv->bit_depth, (uint64_t)lv->sample_bytes,
                                (uint64_t)lv->shift});
@@ -912,8 +914,10 @@ extern "C" int dmmt_ycc_matrix_coefficients(int32_t matrix, float m[6]) {
     return DMMT_OK;
 }
 
-extern "C" int dmmt_encode_device_ycc_matrix(dmmt_ctx* c, const dmmt_device_ycc* y, const dmmt_ycc_levels* levels,
-                                             int32_t matrix, const dmmt_options* opt, void* stream) {
+// dmmt_encode_device_ycc_matrix, and with `subsample` dmmt_encode_device_ycc_subsample:
+// the planes may lie at a finer sampling than the file's
+static int encode_device_ycc(dmmt_ctx* c, const dmmt_device_ycc* y, const dmmt_ycc_levels* levels, int32_t matrix,
+                             const dmmt_options* opt, void* stream, bool subsample) {
     c = primary(c);
     if (!c || !y) return DMMT_E_INVALID_ARGUMENT;
     // JFIF: the planes are written as they are, by the kernels and under the graph keys of
@@ -925,7 +929,13 @@ extern "C" int dmmt_encode_device_ycc_matrix(dmmt_ctx* c, const dmmt_device_ycc*
     if ((rc = validate(opt))) return rc;
     if (y->n_frames <= 0 || !y->d_out || !y->d_out_len) return DMMT_E_INVALID_ARGUMENT;
     if (y->format < DMMT_YCC_PLANAR || y->format > DMMT_YCC_NV_VU) return DMMT_E_INVALID_ARGUMENT;
-    if (y->chroma_sampling != opt->subsampling) return DMMT_E_INVALID_ARGUMENT;  // no conversion between samplings
+    // the planes' rates (shr, svr); those of the file are g's.  Only the subsample call converts,
+    // and only to a coarser file: 4:4:4 -> 4:2:2 / 4:2:0, 4:2:2 -> 4:2:0
+    int shr, svr, fhr, fvr;
+    if (!ycc_rates(y->chroma_sampling, &shr, &svr) || !ycc_rates(opt->subsampling, &fhr, &fvr))
+        return DMMT_E_INVALID_ARGUMENT;
+    const bool converting = y->chroma_sampling != opt->subsampling;
+    if (converting && (!subsample || fhr % shr || fvr % svr || fhr < shr || fvr < svr)) return DMMT_E_INVALID_ARGUMENT;
     const YccLevels lv = ycc_levels_of(levels);
     if (!ycc_levels_valid(lv)) return DMMT_E_INVALID_ARGUMENT;
     const size_t sb = (size_t)lv.sample_bytes;
@@ -934,7 +944,7 @@ extern "C" int dmmt_encode_device_ycc_matrix(dmmt_ctx* c, const dmmt_device_ycc*
         if (!y->d_plane[p] || (uintptr_t)y->d_plane[p] % sb) return DMMT_E_INVALID_ARGUMENT;
     Geom g;
     if ((rc = make_checked_geom(y->width, y->height, opt->subsampling, 255, opt->restart_interval, &g))) return rc;
-    const size_t chroma_row = (size_t)((g.width + g.hr - 1) / g.hr) * (y->format == DMMT_YCC_PLANAR ? 1 : 2) * sb;
+    const size_t chroma_row = (size_t)((g.width + shr - 1) / shr) * (y->format == DMMT_YCC_PLANAR ? 1 : 2) * sb;
     if (y->luma_pitch < (size_t)g.width * sb || y->luma_pitch > DMMT_MAX_ROW_PITCH || y->chroma_pitch < chroma_row ||
         y->chroma_pitch > DMMT_MAX_ROW_PITCH)
         return DMMT_E_INVALID_ARGUMENT;
@@ -944,6 +954,7 @@ extern "C" int dmmt_encode_device_ycc_matrix(dmmt_ctx* c, const dmmt_device_ycc*
     for (int p = 0; p < nplanes; ++p) yf.plane[p] = y->d_plane[p];
     yf.luma_pitch = y->luma_pitch, yf.chroma_pitch = y->chroma_pitch;
     yf.format = y->format;
+    if (converting) yf.src_hr = shr, yf.src_vr = svr;  // (else 0: the same kernels and graph keys as ever)
     // uint8 full range is k_front_ycc's contract: the same kernel, the same graph key
     const bool plain = lv.range == YCC_RANGE_FULL && lv.sample_bytes == 1;
     // (the context's view of the samples stays "8-bit, maxval 255" whatever the levels:
@@ -957,6 +968,16 @@ extern "C" int dmmt_encode_device_ycc_matrix(dmmt_ctx* c, const dmmt_device_ycc*
     if (convert)  // (the matrix kernel takes every levels, uint8 full range included)
         return encode_device_frames(c, &f, opt, stream, g, nullptr, &yf, nullptr, &lv, &mx, matrix);
     return encode_device_frames(c, &f, opt, stream, g, nullptr, &yf, nullptr, plain ? nullptr : &lv);
+}
+
+extern "C" int dmmt_encode_device_ycc_matrix(dmmt_ctx* c, const dmmt_device_ycc* y, const dmmt_ycc_levels* levels,
+                                             int32_t matrix, const dmmt_options* opt, void* stream) {
+    return encode_device_ycc(c, y, levels, matrix, opt, stream, false);
+}
+
+extern "C" int dmmt_encode_device_ycc_subsample(dmmt_ctx* c, const dmmt_device_ycc* y, const dmmt_ycc_levels* levels,
+                                                int32_t matrix, const dmmt_options* opt, void* stream) {
+    return encode_device_ycc(c, y, levels, matrix, opt, stream, true);
 }
 
 extern "C" int dmmt_encode_device_ycc_levels(dmmt_ctx* c, const dmmt_device_ycc* y, const dmmt_ycc_levels* levels,

@@ -1,5 +1,6 @@
 // front_common.hpp -- the device code the front kernels share (kernels.hip:
-// k_front, k_front_surf; front_ycc.hip: k_front_ycc; front_gray.hip: k_front_gray,
+// k_front, k_front_surf; front_ycc.hip: k_front_ycc; front_ycc_sub.hip: k_front_ycc_sub;
+// front_gray.hip: k_front_gray,
 // and their narrow twins): the tile's block geometry, the plane accessor of the
 // chunk loaders, the staging copy, the quantiser tables' LDS fill, the column pass
 // with the blocks' store.  What differs between the kernels -- how a tile's bytes

@@ -1,5 +1,6 @@
 // front_launch.hpp -- the grid and the launch of a front kernel (kernels.hip:
-// k_front, k_front_surf; front_ycc.hip: k_front_ycc; front_gray.hip: k_front_gray;
+// k_front, k_front_surf; front_ycc.hip: k_front_ycc; front_ycc_sub.hip: k_front_ycc_sub;
+// front_gray.hip: k_front_gray;
 // each with a narrow twin, *_n): host code shared by their launchers.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -32,7 +32,7 @@
 // its instantiations unpack no shift and carry no transfer constants.
 //
 // The chroma planes are taken as they lie, ceil(W / HR) x ceil(H / VR), never
-// resampled or averaged.  The padding is padder.rs:12-42's black in YCbCr up to the
+// resampled or averaged (planes finer than the file: front_ycc_sub.hip).  The padding is padder.rs:12-42's black in YCbCr up to the
 // MCU multiple, luma -128 and chroma 0: the loader (ycc_load.hpp) stages the
 // samples that become just that past the rectangle -- plain 0 and 0x80, levels and
 // matrix the codes offY << shift and offC << shift, which transfer to y = -128 and
@@ -52,55 +52,15 @@
 #include "device_common.hpp"
 #include "front_common.hpp"
 #include "front_launch.hpp"
+#include "front_ycc_common.hpp"
 #include "jpeg_common.hpp"
 #include "kernels.hpp"
 #include "ycc_load.hpp"
 
 namespace dmmt {
 
-enum { YCC_IN_PLAIN = 0, YCC_IN_LEVELS = 1, YCC_IN_MATRIX = 2 };
-
-// The kernel's first argument, one struct per kind: the planes of frame 0 (three
-// pointers as values: an indexed read of a kernel argument would put it into
-// scratch) and their description; the sample levels; the matrix.
-struct YccArgs {
-    static constexpr int IN = YCC_IN_PLAIN;
-    const uint8_t *p0, *p1, *p2;  // Y; Cb or the pairs; Cr (planar only)
-    YccDesc d;
-};
-struct YccCodes {
-    uint32_t luma_fill, chroma_fill;  // the pad codes << shift, in every sample of a word
-    uint32_t shift;                   // unused low bits of a uint16 sample
-    uint32_t max_code;                // 2^B - 1
-};
-struct YccLvArgs : YccArgs {
-    static constexpr int IN = YCC_IN_LEVELS;
-    YccTransfer t;
-    YccCodes c;
-};
-struct YccMxArgs : YccArgs {
-    static constexpr int IN = YCC_IN_MATRIX;
-    YccTransfer t;
-    YccMatrix m;
-    YccCodes c;
-};
-struct YccMems {
-    const uint8_t *p0, *p1, *p2;
-    __device__ __forceinline__ PlaneMem plane(int p) const { return PlaneMem{p == 0 ? p0 : (p == 1 ? p1 : p2)}; }
-};
-
-// a code -> the level-shifted full-range value (plain: the code is the sample)
-template <int IN>
-__device__ __forceinline__ float ycc_luma_in(uint32_t v, const YccTransfer& t) {
-    if constexpr (IN == YCC_IN_PLAIN) return (float)v - 128.0f;
-    return fminf(fmaxf(((float)v - t.off_y) * t.k_y, 0.0f), 255.0f) - 128.0f;
-}
-template <int IN>
-__device__ __forceinline__ float ycc_chroma_in(uint32_t v, const YccTransfer& t) {
-    if constexpr (IN == YCC_IN_PLAIN) return (float)v - 128.0f;
-    return fminf(fmaxf(((float)v - t.off_c) * t.k_c, -128.0f), 127.0f);
-}
-__device__ __forceinline__ float ycc_clamp(float v) { return fminf(fmaxf(v, -128.0f), 127.0f); }
+// (The argument structs, YccArgs / YccLvArgs / YccMxArgs, and the transfer functions:
+// front_ycc_common.hpp, shared with front_ycc_sub.hip.)
 
 // One workgroup (256 threads) per tile = TM horizontally adjacent MCUs of one MCU
 // row (256 luma columns, 8 * VR luma rows), a grid-stride loop over the frame's
@@ -498,34 +458,6 @@ constexpr int front_ycc_wpe() {
     return SB == 2 && !(HR == 2 && VR == 1) ? 3 : 4;
 }
 
-// the kernel's first argument for frames yf (lv: null for YccArgs; else valid)
-template <class Args>
-static Args ycc_args(const YccFrames& yf, const YccLevels* lv, const Geom& g) {
-    const int sb = lv ? lv->sample_bytes : 1;
-    Args ya{};
-    ya.p0 = (const uint8_t*)yf.plane[0];
-    ya.p1 = (const uint8_t*)yf.plane[1];
-    ya.p2 = (const uint8_t*)yf.plane[yf.format == YCC_PLANAR ? 2 : 1];
-    ya.d.luma_pitch = (long long)yf.luma_pitch;
-    ya.d.chroma_pitch = (long long)yf.chroma_pitch;
-    ya.d.luma_span = (long long)ycc_plane_span_levels(yf.format, 0, g.width, g.height, g.hr, g.vr, yf.luma_pitch,
-                                                      yf.chroma_pitch, sb);
-    ya.d.chroma_span = (long long)ycc_plane_span_levels(yf.format, 1, g.width, g.height, g.hr, g.vr, yf.luma_pitch,
-                                                        yf.chroma_pitch, sb);
-    ya.d.width = g.width, ya.d.height = g.height;
-    ya.d.cw = (g.width + g.hr - 1) / g.hr, ya.d.ch = (g.height + g.vr - 1) / g.vr;
-    if constexpr (Args::IN != YCC_IN_PLAIN) {
-        ya.t = ycc_levels_transfer(*lv);
-        // the pad codes: offY and offC are integers below 2^B, so << shift stays inside 16 (8) bits
-        const uint32_t py = (uint32_t)ya.t.off_y << lv->shift, pc = (uint32_t)ya.t.off_c << lv->shift;
-        ya.c.luma_fill = sb == 1 ? py * 0x01010101u : py * 0x00010001u;
-        ya.c.chroma_fill = sb == 1 ? pc * 0x01010101u : pc * 0x00010001u;
-        ya.c.shift = (uint32_t)lv->shift;
-        ya.c.max_code = (1u << lv->bit_depth) - 1u;
-    }
-    return ya;
-}
-
 // the instantiation for (format, sb, g's sampling): the plain kind has uint8 ones only
 template <class Args>
 static void front_ycc_dispatch(const Args& ya, int format, int sb, size_t frame_stride, int n_frames, const Geom& g,
@@ -560,15 +492,17 @@ hipError_t launch_front_ycc(const YccFrames& yf, const YccLevels* lv, const YccM
                             int n_frames, const Geom& g, const Work& w, hipStream_t st, int per_cu_cap) {
     if (yf.format < YCC_PLANAR || yf.format > YCC_NV_VU || (lv && !ycc_levels_valid(*lv)) || (mx && !lv))
         return hipErrorInvalidValue;
+    if (yf.src_hr)  // planes at a finer sampling than the file's: front_ycc_sub.hip
+        return launch_front_ycc_sub(yf, lv, mx, frame_stride_bytes, n_frames, g, w, st, per_cu_cap);
     const int sb = lv ? lv->sample_bytes : 1;
     if (mx) {
-        YccMxArgs ya = ycc_args<YccMxArgs>(yf, lv, g);
+        YccMxArgs ya = ycc_args<YccMxArgs>(yf, lv, g, g.hr, g.vr);
         ya.m = *mx;
         front_ycc_dispatch(ya, yf.format, sb, frame_stride_bytes, n_frames, g, w, st, per_cu_cap);
     } else if (lv) {
-        front_ycc_dispatch(ycc_args<YccLvArgs>(yf, lv, g), yf.format, sb, frame_stride_bytes, n_frames, g, w, st, per_cu_cap);
+        front_ycc_dispatch(ycc_args<YccLvArgs>(yf, lv, g, g.hr, g.vr), yf.format, sb, frame_stride_bytes, n_frames, g, w, st, per_cu_cap);
     } else {
-        front_ycc_dispatch(ycc_args<YccArgs>(yf, nullptr, g), yf.format, sb, frame_stride_bytes, n_frames, g, w, st,
+        front_ycc_dispatch(ycc_args<YccArgs>(yf, nullptr, g, g.hr, g.vr), yf.format, sb, frame_stride_bytes, n_frames, g, w, st,
                            per_cu_cap);
     }
     return hipGetLastError();

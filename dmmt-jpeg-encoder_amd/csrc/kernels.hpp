@@ -62,6 +62,9 @@ struct YccFrames {
     const void* plane[3];  // Y; Cb or the plane of pairs; Cr (planar only)
     size_t luma_pitch, chroma_pitch;
     int format;
+    // the rates the chroma planes lie at when finer than the file's (g.hr, g.vr), the
+    // converting pairs of dmmt_encode_device_ycc_subsample; 0, 0: the file's
+    int src_hr, src_vr;
 };
 // bytes from the first byte of `plane` to one past its last, per frame; 0: a bad
 // format or a plane the format does not use
@@ -99,9 +102,15 @@ bool ycc_matrix_coefficients(int matrix, YccMatrix* out);
 // k_front_ycc (front_ycc.hip): the planes -> w.coef, as launch_front; their chroma
 // sampling is g's.  lv null: uint8 full range (the plain instantiations); else any
 // valid levels, and a code above 2^bits - 1 raises status bit 1.  mx (needs lv):
-// that step after the transfer; null: none
+// that step after the transfer; null: none.  yf.src_hr set: the planes lie at (src_hr,
+// src_vr), one of 4:4:4 -> 4:2:2, 4:4:4 -> 4:2:0, 4:2:2 -> 4:2:0, and k_front_ycc_sub
+// (front_ycc_sub.hip, launch_front_ycc_sub) box-averages their chroma to g's sampling
 hipError_t launch_front_ycc(const YccFrames& yf, const YccLevels* lv, const YccMatrix* mx, size_t frame_stride_bytes,
                             int n_frames, const Geom& g, const Work& w, hipStream_t st, int per_cu_cap = 0);
+// what launch_front_ycc forwards to when yf.src_hr is set (hipErrorInvalidValue: no converting pair)
+hipError_t launch_front_ycc_sub(const YccFrames& yf, const YccLevels* lv, const YccMatrix* mx,
+                                size_t frame_stride_bytes, int n_frames, const Geom& g, const Work& w, hipStream_t st,
+                                int per_cu_cap = 0);
 
 // A one-channel plane (dmmt_device_gray): transfer as dmmt_gray_transfer
 enum { GRAY_AS_RGB = 0, GRAY_Y_FULL_RANGE = 1 };

@@ -5,7 +5,8 @@
 //
 // A tile is 256 luma columns by 8 * VR luma rows of one frame.  Its bytes:
 //  * 8 * VR luma tile rows of 256 bytes from the Y plane (luma_pitch);
-//  * 8 chroma tile rows per chroma plane, 256 / HR positions each: one byte per
+//  * 8 chroma tile rows per chroma plane (more for planes finer than the file, see
+//    YccTile), 256 / HR positions each: one byte per
 //    position from the Cb and from the Cr plane (planar), or two bytes per position
 //    -- a Cb,Cr or Cr,Cb pair -- from the one chroma plane (NV); chroma_pitch.
 // Every tile row is fetched as the aligned 16-byte chunks that cover it at its own
@@ -40,28 +41,36 @@ struct YccDesc {
 
 // Tile geometry.  NV: the chroma plane holds pairs.  Chunk q of a tile: the luma
 // chunks first (tile row q / LRC, chunk q % LRC of it), then the chroma tile rows
-// (plane-major: all 8 rows of Cb, then of Cr), CRC chunks each.
-template <int HR_, int VR_, bool NV_, int SB_ = 1>
+// (plane-major: all CROWS rows of Cb, then of Cr), CRC chunks each.
+//
+// SHR, SVR: the rates the chroma planes lie at, the file's (HR, VR) unless the kernel
+// box-averages finer planes to the file's sampling (front_ycc_sub.hip): a chroma tile
+// row then holds 256 / SHR positions and a chroma plane CROWS = 8 * VR / SVR tile rows,
+// the plane rows under the tile's 8 * VR luma rows.
+template <int HR_, int VR_, bool NV_, int SB_ = 1, int SHR_ = HR_, int SVR_ = VR_>
 struct YccTile {
     static_assert(SB_ == 1 || SB_ == 2, "uint8 or uint16 samples");
-    static constexpr int HR = HR_, VR = VR_, SB = SB_;
+    static_assert(HR_ % SHR_ == 0 && VR_ % SVR_ == 0, "the planes are as fine as the file or finer");
+    static constexpr int HR = HR_, VR = VR_, SB = SB_, SHR = SHR_, SVR = SVR_;
     static constexpr bool NV = NV_;
     static constexpr int ROWS = 8 * VR;               // luma tile rows
     static constexpr int LRB = 256 * SB;              // bytes of a luma tile row
     static constexpr int LRC = LRB / 16 + 1;          // its chunks at any misalignment
     static constexpr int LRS = LRC * 16;              // its stride in LDS
-    static constexpr int CPX = 256 / HR;              // chroma positions of a tile row
+    static constexpr int CPX = 256 / SHR;             // chroma positions of a tile row
+    static constexpr int CROWS = 8 * VR / SVR;        // chroma tile rows per plane: 8 or 16
+    static constexpr int CSH = CROWS == 8 ? 3 : 4;    // log2 of it
     static constexpr int CBPP = (NV ? 2 : 1) * SB;    // bytes per chroma position of a plane
     static constexpr int CRB = CPX * CBPP, CRC = CRB / 16 + 1, CRS = CRC * 16;
     static constexpr int NCPL = NV ? 1 : 2;           // chroma planes
     static constexpr int NLC = ROWS * LRC;            // luma chunks
-    static constexpr int NCHUNK = NLC + 8 * NCPL * CRC;
+    static constexpr int NCHUNK = NLC + CROWS * NCPL * CRC;
     static constexpr int NQ = (NCHUNK + 255) / 256;   // chunks per thread
     static constexpr int BYTES = NCHUNK * 16;
     static constexpr int C_OFF = NLC * 16;            // LDS offset of the first chroma tile row
     // LDS offset of luma tile row ly / of chroma tile row r of chroma plane cp
     static constexpr int luma_row(int ly) { return ly * LRS; }
-    static constexpr int chroma_row(int cp, int r) { return C_OFF + (cp * 8 + r) * CRS; }
+    static constexpr int chroma_row(int cp, int r) { return C_OFF + (cp * CROWS + r) * CRS; }
 };
 
 // the samples of the tile row at position px0 that lie inside a plane `width` wide
@@ -84,16 +93,16 @@ DMMT_SURF_FN void ycc_fill_from(uint32_t (&w)[4], long long n, uint32_t fill) {
 
 // Every chunk of the tile at (x0, y0) is a whole load inside its plane's span:
 // the tile lies inside the luma rectangle -- and so inside the chroma rectangle,
-// x0 and y0 being multiples of 256 and 8 * VR -- and away from the planes' first and
-// last bytes.
+// x0 and y0 being multiples of 256 and 8 * VR, which SHR and SVR divide -- and away
+// from the planes' first and last bytes.
 template <class T>
 DMMT_SURF_FN bool ycc_tile_interior(const YccDesc& d, int x0, int y0) {
     if (x0 + 256 > d.width || y0 + T::ROWS > d.height) return false;
-    const int cx0 = x0 / T::HR, cy0 = y0 / T::VR;
+    const int cx0 = x0 / T::SHR, cy0 = y0 / T::SVR;
     return surf_interior(surf_row_start(d.luma_pitch, T::SB, x0, y0),
                          surf_row_start(d.luma_pitch, T::SB, x0, y0 + T::ROWS - 1), T::LRB, d.luma_span) &&
            surf_interior(surf_row_start(d.chroma_pitch, T::CBPP, cx0, cy0),
-                         surf_row_start(d.chroma_pitch, T::CBPP, cx0, cy0 + 7), T::CRB, d.chroma_span);
+                         surf_row_start(d.chroma_pitch, T::CBPP, cx0, cy0 + T::CROWS - 1), T::CRB, d.chroma_span);
 }
 
 // Chunk q < NCHUNK of the tile at (x0, y0) as staged.  Mems:
@@ -108,10 +117,10 @@ DMMT_SURF_FN void ycc_tile_chunk(const Mems& ms, const YccDesc& d, int x0, int y
     const int qc = luma ? q : q - T::NLC;
     const int rc = luma ? T::LRC : T::CRC;
     const int tr = qc / rc, j = qc - tr * rc;
-    const int p = luma ? 0 : 1 + (tr >> 3);
+    const int p = luma ? 0 : 1 + (tr >> T::CSH);
     const int bpp = luma ? T::SB : T::CBPP;
-    const int px0 = luma ? x0 : x0 / T::HR;
-    const int py = luma ? y0 + tr : y0 / T::VR + (tr & 7);
+    const int px0 = luma ? x0 : x0 / T::SHR;
+    const int py = luma ? y0 + tr : y0 / T::SVR + (tr & (T::CROWS - 1));
     const long long pitch = luma ? d.luma_pitch : d.chroma_pitch;
     const auto& m = ms.plane(p);
     const long long start = surf_row_start(pitch, bpp, px0, py);

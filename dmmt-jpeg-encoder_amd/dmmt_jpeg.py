@@ -96,6 +96,7 @@ def lib():
     L.dmmt_ycc_plane_span_levels.restype = sz
     L.dmmt_encode_device_ycc_matrix.argtypes = [vp, P(DmmtDeviceYcc), P(DmmtYccLevels), i32, P(DmmtOptions), vp]
     L.dmmt_ycc_matrix_coefficients.argtypes = [i32, P(ctypes.c_float)]
+    L.dmmt_encode_device_ycc_subsample.argtypes = [vp, P(DmmtDeviceYcc), P(DmmtYccLevels), i32, P(DmmtOptions), vp]
     L.dmmt_encode_device_gray.argtypes = [vp, P(DmmtDeviceGray), P(DmmtOptions), vp]
     L.dmmt_gray_span.argtypes = [P(DmmtDeviceGray)]
     L.dmmt_gray_span.restype = sz
@@ -669,15 +670,25 @@ class Encoder:
                           height: int, options: JpegTransformationOptions, d_out: int, out_stride: int,
                           d_out_len: int, frame_stride: int = 0, stream: int | None = None,
                           opt_c: DmmtOptions | None = None, levels: DmmtYccLevels | None = None,
-                          matrix: int = YccMatrix.JFIF):
+                          matrix: int = YccMatrix.JFIF, chroma_sampling: int | None = None):
         """dmmt_encode_device_ycc: uint8 full-range YCbCr planes in HBM, subsampled as
         options.chroma_subsampling_preset says; enqueued, see synchronize().  levels:
         dmmt_encode_device_ycc_levels -- limited range, 8 to 16 bits in uint16 samples
         (pitches and frame_stride stay in bytes).  matrix: dmmt_encode_device_ycc_matrix --
-        BT709 or BT2020 planes are taken to the JFIF matrix on the way"""
+        BT709 or BT2020 planes are taken to the JFIF matrix on the way.  chroma_sampling:
+        dmmt_encode_device_ycc_subsample -- the preset the planes lie at (chroma_pitch too),
+        as fine as the file's or finer: their chroma is box-averaged to the file's sampling;
+        None: the options' preset, the calls above"""
         opt = opt_c if opt_c is not None else options.to_c()
-        y = self.ycc(d_planes, fmt, luma_pitch, chroma_pitch, n_frames, width, height, opt.subsampling, d_out,
-                     out_stride, d_out_len, frame_stride)
+        y = self.ycc(d_planes, fmt, luma_pitch, chroma_pitch, n_frames, width, height,
+                     opt.subsampling if chroma_sampling is None else int(chroma_sampling), d_out, out_stride,
+                     d_out_len, frame_stride)
+        if chroma_sampling is not None:
+            _check(lib().dmmt_encode_device_ycc_subsample(self._ctx, ctypes.byref(y),
+                                                          ctypes.byref(levels) if levels is not None else None,
+                                                          int(matrix), ctypes.byref(opt), stream),
+                   "encode_device_ycc_subsample")
+            return
         if int(matrix) != YccMatrix.JFIF:
             _check(lib().dmmt_encode_device_ycc_matrix(self._ctx, ctypes.byref(y),
                                                        ctypes.byref(levels) if levels is not None else None,
@@ -692,14 +703,17 @@ class Encoder:
 
     def encode_ycc(self, y, cb=None, cr=None, uv=None, vu=None, options: JpegTransformationOptions = None,
                    bit_depth: int = 8, shift: int = 0, range: int = YccRange.FULL,
-                   matrix: int = YccMatrix.JFIF) -> bytes:
+                   matrix: int = YccMatrix.JFIF, chroma_sampling: int | None = None) -> bytes:
         """One frame from host planes (numpy uint8, JFIF full range): y (H, W) with cb
         and cr (ch, cw) each, or uv / vu (ch, cw, 2) -- Cb,Cr / Cr,Cb pairs; ch =
         ceil(H / vr), cw = ceil(W / hr) for options.chroma_subsampling_preset.  The
         planes are uploaded, encoded where they lie (no RGB round trip) and freed.
         Other levels: range=YccRange.LIMITED, and uint16 planes of bit_depth (8..16)
         significant bits above `shift` unused low bits (P010: bit_depth 10, shift 6).
-        matrix: YccMatrix.BT709 / BT2020 planes are taken to the JFIF matrix."""
+        matrix: YccMatrix.BT709 / BT2020 planes are taken to the JFIF matrix.
+        chroma_sampling: the ChromaSubsamplingPreset the chroma planes lie at when finer
+        than the file's (4:4:4 or 4:2:2 planes for a 4:2:0 file): ch and cw go by it, and
+        the chroma is box-averaged to the file's sampling; None: the options' preset."""
         if options is None:
             options = JpegTransformationOptions()
         given = [k for k, v in (("cb", cb), ("cr", cr), ("uv", uv), ("vu", vu)) if v is not None]
@@ -711,7 +725,8 @@ class Encoder:
             fmt, chroma = YccFormat.NV_VU, [vu]
         else:
             raise ValueError("give cb and cr, or uv, or vu")
-        sub = ChromaSubsamplingPreset(options.chroma_subsampling_preset)
+        file_sub = ChromaSubsamplingPreset(options.chroma_subsampling_preset)
+        sub = file_sub if chroma_sampling is None else ChromaSubsamplingPreset(int(chroma_sampling))
         planes = [np.asarray(p) for p in [y] + chroma]
         dtype = planes[0].dtype
         if dtype not in (np.uint8, np.uint16) or any(p.dtype != dtype for p in planes):
@@ -729,7 +744,7 @@ class Encoder:
         for p in planes[1:]:
             if p.shape != want:
                 raise ValueError(f"chroma shape {p.shape}: {want} is required for {w} x {h} {sub.name}")
-        cap = max_jpeg_bytes(w, h, int(sub))
+        cap = max_jpeg_bytes(w, h, int(file_sub))
         ptrs = []
         try:
             for p in planes:
@@ -740,7 +755,8 @@ class Encoder:
             d_len = self.malloc(4)
             ptrs.append(d_len)
             self.encode_device_ycc(ptrs[:len(planes)], fmt, w * sb, planes[1].nbytes // ch, 1, w, h, options, d_out,
-                                   cap, d_len, levels=levels, matrix=matrix)
+                                   cap, d_len, levels=levels, matrix=matrix,
+                                   chroma_sampling=None if chroma_sampling is None else int(sub))
             self.synchronize()
             n = int(np.frombuffer(self.d2h(d_len, 4), np.uint32)[0])
             return self.d2h(d_out, min(n, cap))

@@ -202,8 +202,8 @@ size_t dmmt_surface_span(const dmmt_device_surfaces* surfaces);
  *    (dmmt_encode_device_ycc_levels below converts it, and takes 10- to 16-bit planes);
  *  - the luma plane is width x height, each chroma component ceil(width/hr) x ceil(height/vr).
  *    The chroma is taken as given: no resampling, no averaging.  chroma_sampling says how the
- *    planes lie and must equal opt->subsampling: conversion between samplings is out of
- *    scope (DMMT_E_INVALID_ARGUMENT);
+ *    planes lie and must equal opt->subsampling, else DMMT_E_INVALID_ARGUMENT
+ *    (dmmt_encode_device_ycc_subsample below takes planes finer than the file);
  *  - a sample s enters the DCT as (float)s - 128, the value range color.rs:75-100 produces;
  *  - padding as padder.rs:12-42, black: luma is padded to multiples of 8*hr / 8*vr with
  *    sample 0, chroma to (padded width)/hr x (padded height)/vr with sample 128;
@@ -226,7 +226,8 @@ typedef struct dmmt_device_ycc {
     size_t frame_stride;         /* bytes between frames, the same for every plane */
     int32_t n_frames;
     int32_t format;              /* dmmt_ycc_format */
-    int32_t chroma_sampling;     /* dmmt_subsampling of the planes as they lie; must equal opt->subsampling */
+    int32_t chroma_sampling;     /* dmmt_subsampling of the planes as they lie; must equal opt->subsampling
+                                    (dmmt_encode_device_ycc_subsample: or be finer) */
     uint16_t width, height;      /* the luma rectangle that is encoded */
     uint8_t* d_out; size_t out_stride; uint32_t* d_out_len;   /* as dmmt_device_frames */
 } dmmt_device_ycc;
@@ -330,8 +331,9 @@ size_t dmmt_ycc_plane_span_levels(const dmmt_device_ycc* ycc, const dmmt_ycc_lev
  *    is -128 whatever chroma sample shares its cell (odd widths and heights make such cells),
  *    chroma padding is 0;
  *  - out of scope: primaries and transfer functions (BT.2020 gamut mapping, PQ / HLG) -- only
- *    the matrix is converted --, chroma interpolation or re-siting, conversion between
- *    samplings, and a host entry point for YCbCr planes. */
+ *    the matrix is converted --, chroma interpolation or re-siting, upsampling of chroma
+ *    (dmmt_encode_device_ycc_subsample below averages finer planes down), and a host entry
+ *    point for YCbCr planes. */
 enum dmmt_ycc_matrix {
     DMMT_YCC_MATRIX_JFIF   = 0,  /* BT.601: the planes are written as they are */
     DMMT_YCC_MATRIX_BT709  = 1,
@@ -340,6 +342,47 @@ enum dmmt_ycc_matrix {
 int dmmt_encode_device_ycc_matrix(dmmt_ctx* ctx, const dmmt_device_ycc* ycc, const dmmt_ycc_levels* levels,
                                   int32_t matrix, const dmmt_options* opt, void* stream);
 int dmmt_ycc_matrix_coefficients(int32_t matrix, float m[6]);
+
+/* ---- YCbCr planes finer than the file: 4:4:4 and 4:2:2 planes as 4:2:2 or 4:2:0 files (extension)
+ * 4:2:2 capture and mezzanine video (NV16 / P210 / I422) and 4:4:4 planes of a renderer or a
+ * screen-content decoder (I444 / NV24), written as the small 4:2:0 (or 4:2:2) file without a
+ * repack pass.  dmmt_encode_device_ycc_subsample IS dmmt_encode_device_ycc_matrix in every
+ * respect -- formats, levels (NULL: uint8 full range), matrix, the DMMT_E_VALUE_EXCEEDS_MAX
+ * check, lanes, streams, stripe invalidation, member 0 of a multi-GPU context, restart intervals
+ * -- except this: ycc->chroma_sampling says how the planes lie and opt->subsampling how the file
+ * is written.  With (shr, svr) the planes' rates, (hr, vr) the file's, rx = hr / shr and
+ * ry = vr / svr:
+ *  - equal samplings: the call is dmmt_encode_device_ycc_matrix itself (the same kernels, the
+ *    same bytes).  Converting pairs: 4:4:4 -> 4:2:2 (rx 2, ry 1), 4:4:4 -> 4:2:0 (2, 2),
+ *    4:2:2 -> 4:2:0 (1, 2).  A file finer than the planes (upsampling) is
+ *    DMMT_E_INVALID_ARGUMENT;
+ *  - the planes are described at THEIR sampling: each chroma component is ceil(width/shr) x
+ *    ceil(height/svr), chroma_pitch is at least such a row, dmmt_ycc_plane_span[_levels] go by
+ *    chroma_sampling already, and the read guarantee is the one those spans state.  out_stride
+ *    is checked against dmmt_max_jpeg_bytes at the FILE's sampling.  A region of interest has
+ *    its origin on the planes' chroma grid; the averaging cells are anchored at the
+ *    rectangle's first sample;
+ *  - the values.  Let y, cb, cr be what dmmt_encode_device_ycc_matrix feeds the DCT for these
+ *    planes at the planes' own sampling: transferred, and with a matrix other than JFIF
+ *    converted, the luma sample at (x, y) using the chroma position (x / shr, y / svr).  They
+ *    are padded black after that step -- luma -128 outside width x height up to the file's MCU
+ *    multiple Wp x Hp, chroma 0 up to (Wp/shr) x (Hp/svr).  Luma goes on as it is.  Each
+ *    chroma plane p(x, y) is box-averaged as the reference subsamples the chroma of RGB
+ *    pixels (subsampling.rs:102-236), in IEEE f32, every operation rounded once, in its order
+ *    (x outer, y inner, the sum then divided by the count):
+ *        (rx, ry) = (2, 1):  (p(2i, j) + p(2i+1, j)) / 2
+ *        (rx, ry) = (1, 2):  (p(i, 2j) + p(i, 2j+1)) / 2
+ *        (rx, ry) = (2, 2):  (((p(2i, 2j) + p(2i, 2j+1)) + p(2i+1, 2j)) + p(2i+1, 2j+1)) / 4
+ *    An odd plane width or height averages the last sample with the padding's 0, as the
+ *    reference averages a padded pixel: the count is always rx * ry.  The result lies in
+ *    [-128, 127] and is never rounded to 8 bits;
+ *  - every chroma sample inside the planes' ceil(width/shr) x ceil(height/svr) rectangle
+ *    influences the output and the range check; nothing outside the spans is read, nothing
+ *    outside the rectangles counts;
+ *  - out of scope: upsampling, any filter other than the box, chroma re-siting, packed formats
+ *    (YUY2 / Y210), a host entry point. */
+int dmmt_encode_device_ycc_subsample(dmmt_ctx* ctx, const dmmt_device_ycc* ycc, const dmmt_ycc_levels* levels,
+                                     int32_t matrix, const dmmt_options* opt, void* stream);
 
 /* ---- grayscale frames (extension) -----------------------------------------------------------
  * One-channel frames -- a mono camera, an IR or depth sensor, a scanned page, the Y plane of a
