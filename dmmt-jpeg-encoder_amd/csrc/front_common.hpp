@@ -1,13 +1,15 @@
 // front_common.hpp -- the device code the front kernels share (kernels.hip:
 // k_front, k_front_surf; front_ycc.hip: k_front_ycc; front_ycc_sub.hip: k_front_ycc_sub;
 // front_gray.hip: k_front_gray,
-// and their narrow twins): the tile's block geometry, the plane accessor of the
-// chunk loaders, the staging copy, the quantiser tables' LDS fill, the column pass
-// with the blocks' store.  What differs between the kernels -- how a tile's bytes
-// are fetched and phase A, the samples' way to the row-transformed blocks -- stays
-// in their own files, and so does the tile loop that calls both: each kernel body
-// writes out the same loop (as a function taking the two as callables it cost three
-// of the budgeted instantiations registers).
+// and their narrow twins): the tile's block geometry and the LDS layout of its
+// row-transformed blocks (front_layout.hpp) with the two accessors every kernel
+// goes through, the plane accessor of the chunk loaders, the staging copy, the
+// quantiser tables' LDS fill, the column pass with the blocks' store.  What differs
+// between the kernels -- how a tile's bytes are fetched and phase A, the samples'
+// way to the row-transformed blocks -- stays in their own files, and so does the
+// tile loop that calls both: each kernel body writes out the same loop (as a
+// function taking the two as callables it cost three of the budgeted instantiations
+// registers).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -15,69 +17,30 @@
 #include "coef_format.hpp"
 #include "dct_quant.hpp"
 #include "device_common.hpp"
+#include "front_layout.hpp"
 #include "jpeg_common.hpp"
 
 namespace dmmt {
 
-// A tile: 256 padded pixel columns by 8 * VR rows = TM horizontally adjacent MCUs
-// of one MCU row.  In LDS its row-transformed blocks (sT) lie block-major: the Y
-// blocks first, 32 columns x VR rows, then the Cb and the Cr blocks (NCOMP 3).
-// NCOMP 1: a grayscale frame, HR = VR = 1, an MCU is one Y block.
-template <int HR_, int VR_, int NCOMP_ = 3>
-struct FrontGeom {
-    static_assert(NCOMP_ == 3 || (NCOMP_ == 1 && HR_ == 1 && VR_ == 1), "gray: one block per MCU");
-    static constexpr int HR = HR_, VR = VR_, NCOMP = NCOMP_;
-    static constexpr int TM = 32 / HR;            // MCUs per tile
-    static constexpr int ROWS = 8 * VR;           // pixel rows per tile
-    static constexpr int NLUMA = HR * VR;
-    static constexpr int BPM = NLUMA + NCOMP - 1; // blocks per MCU
-    static constexpr int NB = TM * BPM;           // blocks per tile
-    static constexpr int NYB = 32 * VR;           // Y blocks: 32 columns x VR rows
-    static constexpr int CB = NCOMP == 1 ? 0 : TM;  // chroma blocks per component
-    static constexpr int NQT = NCOMP == 1 ? 1 : 2;  // quantiser tables: luma[, chroma]
-    static constexpr int BS = 72;                 // LDS floats per block: 64 + pad (conflict-free column reads)
-    static constexpr int ST_FLOATS = NB * BS + 4;  // sT
-    static constexpr int JPT = NB * 8 / 256;      // column jobs (block, column) per thread
-    static_assert(NB * 8 % 256 == 0, "JPT column jobs for every thread");
+// (the tile's block geometry and sT's layout: FrontGeom, front_layout.hpp)
 
-    // Block b starts at b * BS + 4 * f(b), f(b) = bit 2 of b, flipped for Cr: the
-    // 16-byte row stores of phase A (ds_write_b128, lanes in groups of 8 on 8
-    // consecutive blocks -- and Cb next to Cr with 4:2:x) start on 8 distinct
-    // 4-bank offsets mod 32, and the column reads of phase C (32 lanes = 4
-    // consecutive blocks x 8 columns) still hit 32 distinct banks.  With the plain
-    // stride the stores were 2-way conflicted.
-    static constexpr int blk_base(int b) { return b * BS + 4 * (((b >> 2) ^ (NCOMP == 3 && b >= NYB + CB ? 1 : 0)) & 1); }
-
-    // the tile's index of LDS block blk in MCU emission order (block_entangler.rs:
-    // 69-77, block_fold_iterator.rs:53-148): per MCU its Y blocks row by row (4:2:0:
-    // TL, TR, BL, BR), then Cb, then Cr.  Gray: el = blk.
-    static constexpr int emit_index(int blk) {
-        if (blk < NYB) return (blk % 32 / HR) * BPM + (blk / 32) * HR + blk % 32 % HR;
-        return blk < NYB + CB ? (blk - NYB) * BPM + NLUMA : (blk - NYB - CB) * BPM + NLUMA + 1;
-    }
-};
-
+// sT's two accessors.  Phase A of every front kernel stores a row-transformed row
+// with front_store_row, the column pass reads a column with front_load_column: the
+// layout (front_layout.hpp) is written down there and nowhere else.
+// row r of block b: two 16-byte stores
 template <class G>
-constexpr bool front_emit_is_permutation() {
-    bool seen[G::NB] = {};
-    for (int b = 0; b < G::NB; ++b) {
-        const int el = G::emit_index(b);
-        if (el < 0 || el >= G::NB || seen[el]) return false;
-        seen[el] = true;
-    }
-    return true;
+__device__ __forceinline__ void front_store_row(float* sT, int b, int r, const float (&v)[8]) {
+    const int q = G::st_quad(b, r, 0);
+    *reinterpret_cast<float4*>(sT + q) = make_float4(v[0], v[1], v[2], v[3]);
+    *reinterpret_cast<float4*>(sT + G::st_second_half(q)) = make_float4(v[4], v[5], v[6], v[7]);
 }
-static_assert(front_emit_is_permutation<FrontGeom<1, 1>>() && front_emit_is_permutation<FrontGeom<2, 1>>() &&
-                  front_emit_is_permutation<FrontGeom<2, 2>>() && front_emit_is_permutation<FrontGeom<1, 1, 1>>(),
-              "every block of a tile goes out once");
-static_assert(FrontGeom<2, 2>::emit_index(0) == 0 && FrontGeom<2, 2>::emit_index(1) == 1 &&
-                  FrontGeom<2, 2>::emit_index(32) == 2 && FrontGeom<2, 2>::emit_index(33) == 3 &&
-                  FrontGeom<2, 2>::emit_index(64) == 4 && FrontGeom<2, 2>::emit_index(80) == 5 &&
-                  FrontGeom<2, 2>::emit_index(2) == 6,
-              "4:2:0: TL, TR, BL, BR, Cb, Cr, the next MCU's TL");
-static_assert(FrontGeom<2, 1>::emit_index(1) == 1 && FrontGeom<2, 1>::emit_index(32) == 2 &&
-                  FrontGeom<1, 1>::emit_index(1) == 3 && FrontGeom<1, 1, 1>::emit_index(31) == 31,
-              "4:2:2: L, R, Cb; 4:4:4: Y, Cb, Cr; gray: raster");
+// column c of block b, rows 0 to 7
+template <class G>
+__device__ __forceinline__ void front_load_column(const float* sT, int b, int c, float (&v)[8]) {
+    const int a0 = G::st_at(b, 0, c);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = sT[G::st_row_of_column(a0, i)];
+}
 
 // One plane of a frame as the chunk loaders read it (surface_load.hpp's
 // surf_load_chunk, ycc_load.hpp, gray_load.hpp): offsets relative to its first byte.
@@ -115,12 +78,15 @@ __device__ __forceinline__ void front_stage(uint8_t* sRaw, int tid, const uint4 
     }
 }
 
-// sQ[64 * NQT]: the quantiser tables; sRQ: 1/q, correctly rounded -- integer samples
+// sQ[64 * NQT]: the quantiser tables (KEEP_Q false: the kernel keeps no copy and hands
+// the column pass qtab itself); sRQ: 1/q, correctly rounded -- integer samples
 // (SCALED): fl(scale_row * fl(1/q)), the row scaling of arai8 folded in
-template <class G, bool SCALED>
+template <class G, bool SCALED, bool KEEP_Q = true>
 __device__ __forceinline__ void front_fill_qtabs(const float* __restrict__ qtab,  // [2][64] natural, as f32
                                                  float* sQ, float* sRQ, int tid) {
-    if (tid < 64 * G::NQT) sQ[tid] = qtab[tid];
+    if constexpr (KEEP_Q) {
+        if (tid < 64 * G::NQT) sQ[tid] = qtab[tid];
+    }
     if (tid < 64 * G::NQT) sRQ[tid] = SCALED ? c_arai_scale[(tid >> 3) & 7] * (1.0f / qtab[tid]) : 1.0f / qtab[tid];
 }
 
@@ -133,9 +99,10 @@ __device__ __forceinline__ void front_fill_qtabs(const float* __restrict__ qtab,
 // coefficients (arai8, quantize_col8); integer samples take quantize_col8_scaled,
 // nan_possible as dct_quant.hpp has it.  (coef, coef_lo and coef_hi are the kernels'
 // __restrict__ parameters; repeating the qualifier here costs k_front_gray's uint16
-// instantiation a register.)
+// instantiation a register.)  q: the quantiser tables, the kernel's copy in LDS or
+// the table in global memory -- only the quantisers' rare exact path reads them.
 template <class G, bool NARROW, bool F32>
-__device__ __forceinline__ void front_column_pass(const float* sT, const float* sQ, const float* sRQ, int tid,
+__device__ __forceinline__ void front_column_pass(const float* sT, const float* qt, const float* sRQ, int tid,
                                                   bool nan_possible, const Geom& g, int frame, int mx0, int my,
                                                   int16_t* coef, int16_t* coef_lo, int8_t* coef_hi) {
     static_assert(!NARROW || !F32, "Image<f32> dots are unbounded: wide blocks");
@@ -150,13 +117,11 @@ __device__ __forceinline__ void front_column_pass(const float* sT, const float* 
         int x[8];
         float mag = 0.0f;  // FOLD: the largest magnitude among the column's hi rows
         {
-            const int qt = G::NQT == 1 || blk < G::NYB ? 0 : 64;
-            const float* q = sQ + qt + col;
-            const float* rq = sRQ + qt + col;
+            const int qo = G::NQT == 1 || blk < G::NYB ? 0 : 64;
+            const float* q = qt + qo + col;
+            const float* rq = sRQ + qo + col;
             float v[8];
-            const float* tb = sT + G::blk_base(blk) + col;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = tb[i * 8];
+            front_load_column<G>(sT, blk, col, v);
             if constexpr (F32) {
                 arai8(v);
                 quantize_col8(v, q, rq, x);

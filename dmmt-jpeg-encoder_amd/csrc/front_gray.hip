@@ -57,8 +57,8 @@ struct GrayArgs {
 // block row (256 columns, 8 rows), a grid-stride loop over the frame's tiles
 // (blockIdx.y = frame) with the next tile's bytes prefetched into registers while
 // this one computes -- k_front's shape, from the same pieces (front_common.hpp):
-// the one-component FrontGeom with k_front's skewed block-major LDS layout of the
-// row-transformed blocks (sT, blk_base), front_stage and front_column_pass.
+// the one-component FrontGeom with k_front's LDS layout of the row-transformed
+// blocks (sT, front_store_row), front_stage and front_column_pass.
 //  staging  GrayTile / gray_tile_chunk (gray_load.hpp): 8 tile rows, each at its own
 //     misalignment; past the rectangle everything stages as 0
 //  A  one thread per (row r, block c): its 8 samples from LDS -- the table's luma
@@ -150,9 +150,7 @@ __device__ __forceinline__ void front_gray_body(const GrayArgs& ga, size_t frame
                 if (check_range) bad |= (int)(smax > (uint32_t)g.maxval);  // status bit 1
             }
             arai8(v);
-            float4* o = reinterpret_cast<float4*>(sT + G::blk_base(c) + r * 8);
-            o[0] = make_float4(v[0], v[1], v[2], v[3]);
-            o[1] = make_float4(v[4], v[5], v[6], v[7]);
+            front_store_row<G>(sT, c, r, v);
         }
         __syncthreads();
         front_column_pass<G, NARROW, SB == 4>(sT, sQ, sRQ, tid, false, g, frame, mx0, my, coef, coef_lo, coef_hi);

@@ -19,11 +19,13 @@ struct FrontCfg {
     int resident, n_cus;
     bool per_cu_env;
 };
+// max_per_cu > 0: at most so many per CU, whatever fits
 template <typename K>
-static FrontCfg front_cfg(K kernel) {
+static FrontCfg front_cfg(K kernel, int max_per_cu) {
     int per_cu = 0, dev = 0, cus = 0;
     bool env = false;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || per_cu < 1) per_cu = 2;
+    if (max_per_cu > 0 && per_cu > max_per_cu) per_cu = max_per_cu;
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
         cus = 256;
@@ -42,21 +44,22 @@ static inline dim3 front_grid(const FrontCfg& cfg, long long ntiles, int n_frame
 // has none) when the call stores narrow blocks (coef_lo set): the twin takes the
 // wide kernel's arguments, then coef_lo and coef_hi.  A tile is 32 / g.hr MCUs.
 // Each kernel's FrontCfg is a function static, computed once (thread-safe
-// initialisation).
-template <auto Kernel, typename... Args>
+// initialisation).  MAX_PER_CU: the kernel's resident workgroups per CU are capped
+// there (0: as many as fit).
+template <auto Kernel, int MAX_PER_CU = 0, typename... Args>
 static void front_launch_one(const Geom& g, int n_frames, int per_cu_cap, hipStream_t st, Args... args) {
-    static const FrontCfg cfg = front_cfg(Kernel);
+    static const FrontCfg cfg = front_cfg(Kernel, MAX_PER_CU);
     const int tm = 32 / g.hr;
     const long long ntiles = (long long)((g.mcux + tm - 1) / tm) * g.mcuy;
     hipLaunchKernelGGL(Kernel, front_grid(cfg, ntiles, n_frames, per_cu_cap), dim3(256), 0, st, args...);
 }
-template <auto Wide, auto Narrow, typename... Args>
+template <auto Wide, auto Narrow, int MAX_PER_CU = 0, typename... Args>
 static void front_launch(const Geom& g, int n_frames, int per_cu_cap, hipStream_t st, int16_t* coef_lo, int8_t* coef_hi,
                          Args... args) {
     if constexpr (!std::is_null_pointer_v<decltype(Narrow)>) {
-        if (coef_lo) return front_launch_one<Narrow>(g, n_frames, per_cu_cap, st, args..., coef_lo, coef_hi);
+        if (coef_lo) return front_launch_one<Narrow, MAX_PER_CU>(g, n_frames, per_cu_cap, st, args..., coef_lo, coef_hi);
     }
-    front_launch_one<Wide>(g, n_frames, per_cu_cap, st, args...);
+    front_launch_one<Wide, MAX_PER_CU>(g, n_frames, per_cu_cap, st, args...);
 }
 
 // f(HR, VR) with the chroma sampling of g as two std::integral_constants: 4:4:4

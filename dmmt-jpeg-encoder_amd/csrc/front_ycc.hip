@@ -67,7 +67,7 @@ namespace dmmt {
 // tiles (blockIdx.y = frame) with the next tile's bytes prefetched into registers
 // while this one computes -- k_front's shape, from the same pieces
 // (front_common.hpp): FrontGeom's LDS layout of the row-transformed blocks (sT,
-// blk_base), front_stage, and front_column_pass with its emission-order index, so
+// front_store_row), front_stage, and front_column_pass with its emission-order index, so
 // the coefficients land where k_front puts them.
 //  staging  YccTile<.., SB> / ycc_tile_chunk (ycc_load.hpp): 8 * VR luma tile rows
 //     and 8 chroma tile rows per chroma plane, each at its own pitch and
@@ -118,7 +118,8 @@ __device__ __forceinline__ void front_ycc_body(const Args& ya, size_t frame_stri
     constexpr bool NV = FMT != YCC_PLANAR;
     constexpr int VU = FMT == YCC_NV_VU ? 1 : 0;
     using T = YccTile<HR, VR, NV, SB>;
-    using G = FrontGeom<HR, VR>;  // the tile's blocks (front_common.hpp)
+    // the tile's blocks (front_layout.hpp); u8 4:4:4 takes sT without padding, as k_front
+    using G = FrontGeom<HR, VR, 3, SB == 1 && HR * VR == 1>;
     constexpr int NYB = G::NYB, CB = G::CB;
     constexpr int SP = HR;  // threads per (chroma row, chroma block): one per luma block column
     static_assert(8 * CB * SP == 256, "one phase-A job per thread");
@@ -206,9 +207,7 @@ __device__ __forceinline__ void front_ycc_body(const Args& ya, size_t frame_stri
                     v[k] = ycc_luma_in<IN>(s, t);
                 }
                 arai8(v);
-                float4* o = reinterpret_cast<float4*>(sT + G::blk_base((ly >> 3) * 32 + c * HR + h) + (ly & 7) * 8);
-                o[0] = make_float4(v[0], v[1], v[2], v[3]);
-                o[1] = make_float4(v[4], v[5], v[6], v[7]);
+                front_store_row<G>(sT, (ly >> 3) * 32 + c * HR + h, (ly & 7), v);
             }
             const int cx0 = x0 / HR, cy = y0 / VR + r;
 #pragma unroll
@@ -243,9 +242,7 @@ __device__ __forceinline__ void front_ycc_body(const Args& ya, size_t frame_stri
                     }
                 }
                 arai8(v);
-                float4* o = reinterpret_cast<float4*>(sT + G::blk_base(NYB + comp * CB + c) + r * 8);
-                o[0] = make_float4(v[0], v[1], v[2], v[3]);
-                o[1] = make_float4(v[4], v[5], v[6], v[7]);
+                front_store_row<G>(sT, NYB + comp * CB + c, r, v);
             }
         }
         if constexpr (IN == YCC_IN_MATRIX) {
@@ -306,9 +303,7 @@ __device__ __forceinline__ void front_ycc_body(const Args& ya, size_t frame_stri
 #pragma unroll
                 for (int k = 0; k < 8; ++k) v[k] = ycc_clamp(m0 * cb[k] + m1 * cr[k]);
                 arai8(v);
-                float4* o = reinterpret_cast<float4*>(sT + G::blk_base(NYB + comp * CB + c) + r * 8);
-                o[0] = make_float4(v[0], v[1], v[2], v[3]);
-                o[1] = make_float4(v[4], v[5], v[6], v[7]);
+                front_store_row<G>(sT, NYB + comp * CB + c, r, v);
             }
             const int nx = d.width - x0 - lx0;  // the job's luma columns inside the rectangle (<= 0: none)
 #pragma unroll
@@ -327,9 +322,7 @@ __device__ __forceinline__ void front_ycc_body(const Args& ya, size_t frame_stri
                     v[k] = k < nk ? yy : -128.0f;
                 }
                 arai8(v);
-                float4* o = reinterpret_cast<float4*>(sT + G::blk_base((ly >> 3) * 32 + c * HR + h) + (ly & 7) * 8);
-                o[0] = make_float4(v[0], v[1], v[2], v[3]);
-                o[1] = make_float4(v[4], v[5], v[6], v[7]);
+                front_store_row<G>(sT, (ly >> 3) * 32 + c * HR + h, (ly & 7), v);
             }
         }
         __syncthreads();
@@ -452,10 +445,17 @@ size_t ycc_plane_span(int format, int plane, int width, int height, int hr, int 
 // registers, so four workgroups per CU although the LDS would hold five -- and 41 KiB
 // with 4:4:4 and 4:2:0, where three workgroups fit a CU's 160 KiB whatever the
 // registers: 3, a budget of 168.  DESIGN.md sections 13 and 14 list what each
-// instantiation takes; none spills.
+// instantiation takes; none spills.  uint8 4:4:4, as k_front's: sT without padding,
+// 32 KiB of LDS, and a budget of 5 (96 registers) that leaves two resident workgroups'
+// neighbours a fifth k_emit workgroup; a lone lane's launch stays at
+// four workgroups per CU (front_ycc_max_per_cu).
 template <int HR, int VR, int SB>
 constexpr int front_ycc_wpe() {
-    return SB == 2 && !(HR == 2 && VR == 1) ? 3 : 4;
+    return SB == 1 && HR * VR == 1 ? 5 : SB == 2 && !(HR == 2 && VR == 1) ? 3 : 4;
+}
+template <int HR, int VR, int SB>
+constexpr int front_ycc_max_per_cu() {
+    return SB == 1 && HR * VR == 1 ? 4 : 0;
 }
 
 // the instantiation for (format, sb, g's sampling): the plain kind has uint8 ones only
@@ -467,10 +467,11 @@ static void front_ycc_dispatch(const Args& ya, int format, int sb, size_t frame_
             constexpr int FMT = decltype(fmt)::value, SB = decltype(sbc)::value;
             constexpr int HR = decltype(hr)::value, VR = decltype(vr)::value, WPE = front_ycc_wpe<HR, VR, SB>();
             if constexpr (Args::IN == YCC_IN_PLAIN)
-                front_launch<k_front_ycc<HR, VR, FMT, WPE>, k_front_ycc_n<HR, VR, FMT, WPE>>(
+                front_launch<k_front_ycc<HR, VR, FMT, WPE>, k_front_ycc_n<HR, VR, FMT, WPE>, front_ycc_max_per_cu<HR, VR, SB>()>(
                     g, n_frames, per_cu_cap, st, w.coef_lo, w.coef_hi, ya, frame_stride, g, w.qtab, w.coef);
             else
-                front_launch<k_front_ycc_lv<Args, HR, VR, FMT, SB, WPE>, k_front_ycc_lv_n<Args, HR, VR, FMT, SB, WPE>>(
+                front_launch<k_front_ycc_lv<Args, HR, VR, FMT, SB, WPE>, k_front_ycc_lv_n<Args, HR, VR, FMT, SB, WPE>,
+                             front_ycc_max_per_cu<HR, VR, SB>()>(
                     g, n_frames, per_cu_cap, st, w.coef_lo, w.coef_hi, ya, frame_stride, g, w.qtab, w.coef, w.status);
         });
     };

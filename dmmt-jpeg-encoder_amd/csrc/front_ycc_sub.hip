@@ -249,9 +249,7 @@ __device__ __forceinline__ void front_ycc_sub_body(const Args& ya, size_t frame_
                     }
                 }
                 arai8(v);
-                float4* o = reinterpret_cast<float4*>(sT + G::blk_base((ly >> 3) * 32 + c * HR + h) + (ly & 7) * 8);
-                o[0] = make_float4(v[0], v[1], v[2], v[3]);
-                o[1] = make_float4(v[4], v[5], v[6], v[7]);
+                front_store_row<G>(sT, (ly >> 3) * 32 + c * HR + h, (ly & 7), v);
             }
             // the thread's component (h = 0: Cb[']; 1: Cr[']) of the block's chroma row r
             [[maybe_unused]] const float m0 = h ? m.e : m.c, m1 = h ? m.f : m.d;
@@ -281,9 +279,7 @@ __device__ __forceinline__ void front_ycc_sub_body(const Args& ya, size_t frame_
                 }
             }
             arai8(v);
-            float4* o = reinterpret_cast<float4*>(sT + G::blk_base(NYB + h * CB + c) + r * 8);
-            o[0] = make_float4(v[0], v[1], v[2], v[3]);
-            o[1] = make_float4(v[4], v[5], v[6], v[7]);
+            front_store_row<G>(sT, NYB + h * CB + c, r, v);
         }
         __syncthreads();
         front_column_pass<G, NARROW, false>(sT, sQ, sRQ, tid, false, g, frame, mx0, my, coef, coef_lo, coef_hi);

@@ -241,8 +241,8 @@ struct SurfTile {
 //  A  colour + subsampling + row DCT, fused: one thread per (chroma row, luma
 //     block column) converts its 8 x VR pixels (raw bytes from LDS), box-averages
 //     the chroma in the reference's sum order and runs the row pass of its VR
-//     luma rows and of the chroma rows in registers -> block-major LDS (stride
-//     BS); with 4:2:x the two threads of a chroma block swap four chroma samples
+//     luma rows and of the chroma rows in registers -> LDS (front_store_row);
+//     with 4:2:x the two threads of a chroma block swap four chroma samples
 //     over DPP and take one chroma row pass each
 //  C  column DCT + quantise (quantize_col8_scaled): one lane per (block, column),
 //     the column's 8 coefficients kept in registers for
@@ -266,9 +266,9 @@ __device__ __forceinline__ void front_body(const Sample* __restrict__ rgb, size_
                                            int16_t* __restrict__ coef, int* __restrict__ status,
                                            int16_t* __restrict__ coef_lo = nullptr,
                                            int8_t* __restrict__ coef_hi = nullptr) {
-    using G = FrontGeom<HR, VR>;  // the tile's blocks (front_common.hpp)
+    // the tile's blocks (front_layout.hpp); u8 4:4:4 takes sT without padding
+    using G = FrontGeom<HR, VR, 3, sizeof(Sample) == 1 && HR * VR == 1>;
     constexpr int ROWS = G::ROWS, NYB = G::NYB, CB = G::CB;
-    auto blk_base = [](int b) { return G::blk_base(b); };
     constexpr int SP = HR;           // threads per (chroma row, chroma block): one per luma block column
     constexpr int NJ = 8 * CB * SP;  // fused jobs (chroma row, chroma block, luma block column): 256
     constexpr int NCS = 8 / SP;      // chroma samples of a job
@@ -283,7 +283,11 @@ __device__ __forceinline__ void front_body(const Sample* __restrict__ rgb, size_
     __shared__ __attribute__((aligned(16))) float sT[G::ST_FLOATS];
     __shared__ __attribute__((aligned(16))) uint8_t sRaw[Raw::BYTES];
     __shared__ float sLut[256];
-    __shared__ float sQ[128];
+    // u8 4:4:4 keeps no copy of the quantiser tables: its LDS then is at most 32,768
+    // bytes, five workgroups per CU, without which the register budget does not bind
+    // (front_wpe below); only the quantiser's rare exact path reads them, from qtab
+    constexpr bool Q_GLOBAL = SB == 1 && HR * VR == 1;
+    __shared__ float sQ[Q_GLOBAL ? 1 : 128];
     __shared__ float sRQ[128];
 
     DMMT_TRACE_START;
@@ -299,7 +303,7 @@ __device__ __forceinline__ void front_body(const Sample* __restrict__ rgb, size_
     } else {
         foff = (size_t)frame * frame_stride;
     }
-    front_fill_qtabs<G, SB != 4>(qtab, sQ, sRQ, tid);
+    front_fill_qtabs<G, SB != 4, !Q_GLOBAL>(qtab, sQ, sRQ, tid);
     if (SB == 1) sLut[tid] = norm_lut[tid];
     int bad = 0;
     const bool check_range = SB != 4 && g.maxval < (SB == 1 ? 255 : 65535);
@@ -449,19 +453,13 @@ __device__ __forceinline__ void front_body(const Sample* __restrict__ rgb, size_
             for (int dy = 0; dy < VR; ++dy) {
                 const int ly = r * VR + dy;
                 arai8(yv[dy]);
-                float4* o = reinterpret_cast<float4*>(sT + blk_base((ly >> 3) * 32 + c * HR + h) + (ly & 7) * 8);
-                o[0] = make_float4(yv[dy][0], yv[dy][1], yv[dy][2], yv[dy][3]);
-                o[1] = make_float4(yv[dy][4], yv[dy][5], yv[dy][6], yv[dy][7]);
+                front_store_row<G>(sT, (ly >> 3) * 32 + c * HR + h, ly & 7, yv[dy]);
             }
             if constexpr (SP == 1) {
                 arai8(cbv);
                 arai8(crv);
-                float4* ob = reinterpret_cast<float4*>(sT + blk_base(NYB + c) + r * 8);
-                ob[0] = make_float4(cbv[0], cbv[1], cbv[2], cbv[3]);
-                ob[1] = make_float4(cbv[4], cbv[5], cbv[6], cbv[7]);
-                float4* orr = reinterpret_cast<float4*>(sT + blk_base(NYB + CB + c) + r * 8);
-                orr[0] = make_float4(crv[0], crv[1], crv[2], crv[3]);
-                orr[1] = make_float4(crv[4], crv[5], crv[6], crv[7]);
+                front_store_row<G>(sT, NYB + c, r, cbv);
+                front_store_row<G>(sT, NYB + CB + c, r, crv);
             } else {
                 // the pair (h = 0, 1) holds chroma samples 0..3 and 4..7 of the row:
                 // h = 0 takes the row pass of Cb, h = 1 that of Cr, each swapping
@@ -476,9 +474,7 @@ __device__ __forceinline__ void front_body(const Sample* __restrict__ rgb, size_
                     fr[4 + k] = h ? crv[k] : recv;
                 }
                 arai8(fr);
-                float4* oc = reinterpret_cast<float4*>(sT + blk_base(NYB + (h ? CB : 0) + c) + r * 8);
-                oc[0] = make_float4(fr[0], fr[1], fr[2], fr[3]);
-                oc[1] = make_float4(fr[4], fr[5], fr[6], fr[7]);
+                front_store_row<G>(sT, NYB + (h ? CB : 0) + c, r, fr);
             }
         };
         if (tid < NJ) {
@@ -489,7 +485,7 @@ __device__ __forceinline__ void front_body(const Sample* __restrict__ rgb, size_
         }
         __syncthreads();
         DMMT_TRACE(0);
-        front_column_pass<G, NARROW, SB == 4>(sT, sQ, sRQ, tid, g.maxval == 0, g, frame, mx0, my, coef, coef_lo, coef_hi);
+        front_column_pass<G, NARROW, SB == 4>(sT, Q_GLOBAL ? qtab : sQ, sRQ, tid, g.maxval == 0, g, frame, mx0, my, coef, coef_lo, coef_hi);
         DMMT_TRACE(2);
     }
 
@@ -1602,12 +1598,35 @@ namespace dmmt {
 #define FRONT_WPE_420 3
 #endif
 
-// Waves per SIMD k_front is compiled for (register budget 512 / WPE): u8 4:4:4
-// and 4:2:2 fit 128 registers, four resident workgroups per CU; the rest keep the
-// allocation the compiler picks.
+#ifndef FRONT_WPE_444
+#define FRONT_WPE_444 5
+#endif
+#ifndef FRONT_WPE_422
+#define FRONT_WPE_422 4
+#endif
+
+// Waves per SIMD k_front is compiled for (register budget 512 / WPE, in steps of 8).
+// u8 4:4:4 fits 96 registers, so that two resident workgroups leave 320 of a SIMD's
+// 512 to the other lanes' kernels, five waves of k_emit<8> ("what fits
+// beside k_front").  The budget only binds where the kernel's LDS allows as many
+// workgroups (five: at most 32,768 bytes): past that the compiler drops it and pads
+// the allocation up to the occupancy the LDS leaves (RGBX 4:4:4, whose staged rows
+// are a third longer).  u8 4:2:2 keeps its 4: it takes 73 to 81 registers and 27 KB,
+// under either target as it is.  The rest keep the allocation the compiler picks.
 template <int HR, int VR, typename S>
 constexpr int front_wpe() {
-    return sizeof(S) == 1 ? (HR * VR == 4 ? FRONT_WPE_420 : 4) : 1;
+    return sizeof(S) == 1 ? (HR * VR == 4 ? FRONT_WPE_420 : HR * VR == 2 ? FRONT_WPE_422 : FRONT_WPE_444) : 1;
+}
+
+// Resident workgroups per CU of a lone lane's launch (front_launch's MAX_PER_CU; 0: as
+// many as fit).  The u8 4:4:4 kernels, the only ones whose occupancy rose with the
+// compact sT, now fit five, but a lone lane keeps the four it had: a 4K frame's 4,050
+// tiles split worse over 1,280 workgroups than over 1,024, and alone k_front_n took
+// 28.3 us at five against 25.2 us at four (profiles/front_coresident_ab.txt, session
+// 1).  The fifth slot is for the other lanes' kernels.
+template <int HR, int VR, typename S>
+constexpr int front_max_per_cu() {
+    return sizeof(S) == 1 && HR * VR == 1 ? 4 : 0;
 }
 
 // (the launch and its resident grid: front_launch, front_with_sampling of
@@ -1623,9 +1642,9 @@ static void front_sub(const void* rgb, size_t stride_elems, int n_frames, const 
                                                            (const S*)rgb, stride_elems, g, w.norm_lut, w.qtab, w.coef,
                                                            w.status);
         else
-            front_launch<k_front<HR, VR, S, WPE>, k_front_n<HR, VR, S, WPE>>(g, n_frames, per_cu_cap, st, w.coef_lo,
-                                                                             w.coef_hi, (const S*)rgb, stride_elems, g,
-                                                                             w.norm_lut, w.qtab, w.coef, w.status);
+            front_launch<k_front<HR, VR, S, WPE>, k_front_n<HR, VR, S, WPE>, front_max_per_cu<HR, VR, S>()>(
+                g, n_frames, per_cu_cap, st, w.coef_lo, w.coef_hi, (const S*)rgb, stride_elems, g, w.norm_lut, w.qtab, w.coef,
+                w.status);
     });
 }
 
@@ -1639,7 +1658,7 @@ static void front_surf_sub(const SurfArgs& sa, size_t frame_stride, int n_frames
                                                                      sa, frame_stride, g, w.norm_lut, w.qtab, w.coef,
                                                                      w.status);
         else
-            front_launch<k_front_surf<HR, VR, S, LAY, WPE>, k_front_surf_n<HR, VR, S, LAY, WPE>>(
+            front_launch<k_front_surf<HR, VR, S, LAY, WPE>, k_front_surf_n<HR, VR, S, LAY, WPE>, front_max_per_cu<HR, VR, S>()>(
                 g, n_frames, per_cu_cap, st, w.coef_lo, w.coef_hi, sa, frame_stride, g, w.norm_lut, w.qtab, w.coef,
                 w.status);
     });
